@@ -24,15 +24,28 @@ matrix-core products) and codec, GEMMs on h3 split-fp16 operands (fp32-accurate,
 The random weights have bf16 VALUES held in fp32 tensors by default (``--weight-values``): that is what the reference
 computes with, since the HF Qwen2-0.5B checkpoint stores bf16 (``torch_dtype: bfloat16``) and the reference upcasts
 it to fp32.  Such weights are exact in fp16 after scaling, so their h3 GEMMs need two fp16 products instead of three
-(the third is exactly zero).  Separately timed runs: the same fp32 run on full-fp32 random weight values
-(``value_fp32_weights``, ``--no-fp32-weights`` skips it) and the bf16 mode (``value_bf16``, ``--no-bf16``).
+(the third is exactly zero).
+
+A plain run does only what the headline needs: it sets up, warms up, times ``--steps`` steps, writes its outputs if
+``--dump-outputs DIR`` is given and prints the JSON line.  ``--full`` adds the separately timed measurements and
+checks: the same fp32 run on full-fp32 random weight values (``value_fp32_weights``, ``--no-fp32-weights`` skips it),
+the bf16 mode (``value_bf16``, ``--no-bf16``), at N = 1 the reference's notebook sweep and the HF-eager reference path
+on the same GPU, the box calibration, and at N > 1 the p2p probe of every pipeline edge, the N-stage pipeline
+(``value_ppN``) and the per-transport check.
+
+``--dump-outputs DIR`` writes what the timed path returned in its last timed step: ``DIR/window_nll.npy``, the
+per-window NLL ``[micro-batch, window]`` of every ``run_batch`` call of that step (float32 or float64, as the
+pipeline returned it).  Across GPUs (pp > 1 over ranks) the timed region is one continuous pipeline, whose caller
+receives the accumulated NLL: every last-stage rank writes ``DIR/nll_sum.rank<r>.npy`` = [total NLL, scored tokens].
+The token stream and the weights are seeded (``--seed``), so equal arguments give equal inputs from run to run.
 
 ``value`` = window tokens processed per second over the whole job (every window is a full 512-token forward, as in
 the reference, except that the model's last layer, which feeds only the LM head, runs its O-projection / MLP on the
 scored rows: identical NLL, ``config.last_layer_rows``); scored tokens/s, PPL and the wire bytes/token measured by the
 senders' byte counters are reported alongside, plus a per-stage GPU time breakdown for pipelines across GPUs.  At
-N > 1 the headline pp2 x dp(N/2) run is followed by one N-stage pipeline over all the GPUs (``value_ppN``, BASELINE
-configs 4-5), reported beside it.  Data: synthetic token stream of the WikiText-2 test length, random-init
+N > 1 with ``--full`` the headline pp2 x dp(N/2) run is followed by one N-stage pipeline over all the GPUs
+(``value_ppN``, BASELINE configs 4-5), reported beside it.  Data: synthetic token stream of the WikiText-2 test
+length, random-init
 weights of the exact Qwen2-0.5B architecture (no network / HF cache on the benchmark machines), so the PPL is that
 of random weights (~vocab size) and measures plumbing, not quality.
 """
@@ -74,7 +87,13 @@ def parse():
     p.add_argument("--warmup", type=int, default=3)
     p.add_argument("--model", default="qwen2-0.5b")
     p.add_argument("--dtype", default="fp32", choices=sorted(DTYPES))
-    p.add_argument("--no-bf16", action="store_true", help="skip the secondary bf16-mode measurement")
+    p.add_argument("--full", action="store_true",
+                   help="also run the secondary measurements and checks (full-fp32 weight values, bf16 mode, notebook "
+                        "sweep, HF-eager reference path, box calibration; N > 1: p2p probe, N-stage pipeline, "
+                        "transports); the --no-* options below drop single ones of them")
+    p.add_argument("--dump-outputs", default="", metavar="DIR",
+                   help="after the timed steps, write what the timed path returned in its last step as DIR/<name>.npy")
+    p.add_argument("--no-bf16", action="store_true", help="--full: skip the secondary bf16-mode measurement")
     p.add_argument("--batch", type=int, default=64, help="windows per micro-batch")
     p.add_argument("--microbatches", type=int, default=0,
                    help="micro-batches per step per replica (default 4 x pipeline depth across GPUs: every GPU does "
@@ -95,18 +114,19 @@ def parse():
                    help="precision of the random weight VALUES (held in fp32 in the fp32 mode): bf16 = as the HF "
                         "Qwen2-0.5B checkpoint the reference upcasts to fp32 (torch_dtype bfloat16); fp32 = full fp32 "
                         "random values (reported as value_fp32_weights)")
-    p.add_argument("--no-fp32-weights", action="store_true", help="skip the fp32-valued-weights measurement")
+    p.add_argument("--no-fp32-weights", action="store_true", help="--full: skip the fp32-valued-weights measurement")
     p.add_argument("--no-sweep", action="store_true",
-                   help="N = 1: skip the timing of the reference's notebook sweep (notebook_sweep)")
+                   help="--full, N = 1: skip the timing of the reference's notebook sweep (notebook_sweep)")
     p.add_argument("--no-hf-compare", action="store_true",
-                   help="skip the same-node reference-path measurement (HF transformers + eager, N = 1 only)")
+                   help="--full: skip the same-node reference-path measurement (HF transformers + eager, N = 1 only)")
     p.add_argument("--no-deep-pp", action="store_true",
-                   help="N > 1: skip the secondary measurement of one N-stage pipeline over all the GPUs (value_ppN)")
+                   help="--full, N > 1: skip the secondary measurement of one N-stage pipeline over all the GPUs "
+                        "(value_ppN)")
     p.add_argument("--deep-pp-timeout", type=float, default=300.0,
                    help="N > 1: seconds a secondary measurement (deep pipeline, transports) or the shutdown may go "
                         "without progress before it counts as hung")
     p.add_argument("--no-transports", action="store_true",
-                   help="N > 1: skip the short per-transport check (torch p2p / native RCCL / IPC peer copies)")
+                   help="--full, N > 1: skip the short per-transport check (torch p2p / native RCCL / IPC peer copies)")
     p.add_argument("--json-out", default="")
     return p.parse_args()
 
@@ -204,10 +224,11 @@ def build_stage_model(a, env, cfg, dtype, pp, grid, plan, values=None):
                        with_embed=(stage == 0), with_head=(stage == pp - 1), values=values)
 
 
-def measure(a, env, cfg, dtype, pp, grid, plan, timed_steps, warmup, values=None, probe_sizes=(), built=None):
+def measure(a, env, cfg, dtype, pp, grid, plan, timed_steps, warmup, values=None, probe_sizes=(), built=None,
+            dump_dir=""):
     """Build the model/pipeline for ``dtype`` (random weights with ``values`` precision; or use ``built`` =
     ``build_stage_model``'s result, kept alive for the caller) and time ``timed_steps`` steps after ``warmup``.
-    Returns a dict."""
+    ``dump_dir``: write the outputs of the last timed step there (``dump_outputs``).  Returns a dict."""
     dev = env.device
     world = env.world_size
     dist_pp = world > 1 and pp > 1
@@ -236,6 +257,7 @@ def measure(a, env, cfg, dtype, pp, grid, plan, timed_steps, warmup, values=None
     nll_acc = torch.zeros(2, dtype=torch.float64, device=dev)
     per_step = a.microbatches * grid.dp
     reports = []
+    last_step = []   # --dump-outputs: the per-window NLL of every micro-batch of the last timed step
 
     def run_steps(first_step: int, nsteps: int, timing: bool = False):
         """pp across GPUs: one continuous pipeline over all nsteps*microbatches (stages stay busy across step
@@ -244,8 +266,10 @@ def measure(a, env, cfg, dtype, pp, grid, plan, timed_steps, warmup, values=None
         idx = [(first_step * per_step + i) % len(pool) for i in range(nsteps * per_step)]
         if not dist_pp:
             dump = [] if os.environ.get("EDGE_DUMP_NLL") else None
-            for j in idx:
+            for n, j in enumerate(idx):
                 wn = runner.run_batch(pool[j])
+                if dump_dir and timing and n >= len(idx) - per_step:
+                    last_step.append(wn.detach().clone())   # the graph's output buffer is reused by the next call
                 nll_acc[0] += (wn.double() * pool_w[j]).sum()   # device-side accumulation: no host sync
                 nll_acc[1] += pool_w[j].sum()
                 if dump is not None:
@@ -299,6 +323,8 @@ def measure(a, env, cfg, dtype, pp, grid, plan, timed_steps, warmup, values=None
             wires.append(b / t if t else 0.0)
     else:
         wires = runner.wire_bytes_per_token()
+    if dump_dir:
+        dump_outputs(dump_dir, env, last, dist_pp, last_step, nll_acc)
     if dist_pp:
         runner.close()
     del runner, model, built
@@ -306,6 +332,25 @@ def measure(a, env, cfg, dtype, pp, grid, plan, timed_steps, warmup, values=None
     if dev.type == "cuda":
         torch.cuda.empty_cache()
     return {"dt": dt, "ppl": ppl, "prov": prov, "stages": stage_reports, "p2p": probe, "wires": wires}
+
+
+def dump_outputs(path, env, last, dist_pp, last_step, nll_acc, limit=64 << 20) -> None:
+    """``--dump-outputs``: what the timed path handed its caller, as float32 / float64 ``.npy`` files under ``path``.
+    One process: ``window_nll.npy`` [micro-batches of the last timed step, windows].  Pipeline across ranks: every
+    last-stage rank's ``nll_sum.rank<r>.npy`` = [total NLL, scored tokens] of the timed region."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    if not dist_pp:
+        out = torch.stack(last_step) if last_step else torch.zeros(0)
+        out = out if out.dtype in (torch.float32, torch.float64) else out.float()
+        arrays = {"window_nll": out.cpu().numpy()}
+    elif last:
+        arrays = {f"nll_sum.rank{env.rank}": nll_acc.detach().double().cpu().numpy()}
+    else:
+        arrays = {}
+    assert sum(v.nbytes for v in arrays.values()) <= limit, "--dump-outputs: more than 64 MB of outputs"
+    for name, v in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), v)
 
 
 def notebook_sweep(a, env, cfg, dtype, values, windows: int = 64, batch: int = 32) -> dict:
@@ -452,24 +497,24 @@ def main():
     spec = C.get_codec(a.codec)
     msg_bytes = C.message_bytes(spec, a.batch, a.max_length, cfg.hidden_size, a.ratio, dtype)
     main_run = measure(a, env, cfg, dtype, pp, grid, plan, a.steps, a.warmup, values,
-                       probe_sizes=(1 << 20, int(msg_bytes)))
+                       probe_sizes=(1 << 20, int(msg_bytes)) if a.full else (), dump_dir=a.dump_outputs)
     dt = main_run["dt"]
     tok_per_step = grid.dp * a.microbatches * a.batch * a.max_length
     scored_per_step = grid.dp * a.microbatches * a.batch * a.stride
     value = tok_per_step * a.steps / dt
     wires = main_run["wires"]
     second = fp32w = None
-    if values is not None and not a.no_fp32_weights and dtype == torch.float32 and env.device.type == "cuda":
+    if a.full and values is not None and not a.no_fp32_weights and dtype == torch.float32 and env.device.type == "cuda":
         fp32w = measure(a, env, cfg, dtype, pp, grid, plan, a.steps, a.warmup, None)
-    if not a.no_bf16 and dtype == torch.float32 and env.device.type == "cuda":
+    if a.full and not a.no_bf16 and dtype == torch.float32 and env.device.type == "cuda":
         second = measure(a, env, cfg, torch.bfloat16, pp, grid, plan, a.steps, a.warmup, values)
     sweep = None
-    if world == 1 and not a.no_sweep:
+    if a.full and world == 1 and not a.no_sweep:
         sweep = notebook_sweep(a, env, cfg, dtype, values)
     hf = None   # last, so that nothing of it can touch the framework's own measurements
-    if world == 1 and not a.no_hf_compare and env.device.type == "cuda":
+    if a.full and world == 1 and not a.no_hf_compare and env.device.type == "cuda":
         hf = same_node_reference(a, cfg, env.device)
-    calib = box_calibration(env.device) if env.is_main else None
+    calib = box_calibration(env.device) if a.full and env.is_main else None
     dname = {torch.float32: "fp32", torch.bfloat16: "bf16"}[dtype]
     out = {
         "metric": METRIC,
@@ -543,12 +588,12 @@ def main():
     # N > 1: secondary measurements and the shutdown run under one watchdog; a hang anywhere after this point still
     # prints the headline (with the hung measurement marked) and exits 70, an exception is recorded in its field
     guard = Guard(env, emit, a.deep_pp_timeout)
-    if dist_pp and world != pp and not a.no_deep_pp:
+    if a.full and dist_pp and world != pp and not a.no_deep_pp:
         key = f"pp{world}"
         res = guard.run(key, lambda: deep_pipeline(a, env, cfg, dtype, values, spec))
         emit.out[f"value_{key}"] = res.pop("value") if res else None
         emit.out[key] = res if res else {"error": guard.last_error}
-    if dist_pp and not a.no_transports:
+    if a.full and dist_pp and not a.no_transports:
         emit.out["transports"] = transports_check(a, env, cfg, dtype, values, spec, pp, grid, plan, guard)
     emit()
     guard.close()

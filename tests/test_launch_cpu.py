@@ -45,10 +45,10 @@ def _json_line(out):
 @pytest.mark.parametrize("n", [1, 2, 4])
 def test_bench_contract_cpu(n):
     if n == 1:
-        r = subprocess.run([sys.executable] + BENCH + ["--gpus", "1"], cwd=ROOT, env=_env(), capture_output=True,
-                           text=True, timeout=600)
+        r = subprocess.run([sys.executable] + BENCH + ["--gpus", "1", "--full"], cwd=ROOT, env=_env(),
+                           capture_output=True, text=True, timeout=600)
     else:
-        r = _torchrun(n, BENCH + ["--gpus", str(n)])
+        r = _torchrun(n, BENCH + ["--gpus", str(n), "--full"])
     assert r.returncode == 0, r.stderr[-3000:]
     d = _json_line(r.stdout)
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
@@ -92,6 +92,39 @@ def test_bench_contract_cpu(n):
         assert d["sweep_speedup_vs_t4"] == round(16.19 / sw["s_per_window"], 1)
 
 
+def test_bench_plain_run_is_lean_and_dumps_outputs(tmp_path):
+    """Without ``--full`` the run times the headline only (no secondary measurement in the JSON line), ``--steps``
+    sets the number of timed steps, and ``--dump-outputs`` writes the last timed step's per-window NLL: one row per
+    micro-batch, identical from run to run, and equal to the NLL that gives the reported PPL when the step covers
+    the same windows."""
+    import numpy as np
+    outs = []
+    for i, steps in enumerate((1, 1, 3)):
+        d = tmp_path / f"o{i}"
+        r = subprocess.run([sys.executable] + BENCH[:7] + ["--steps", str(steps), "--warmup", "0"] + BENCH[11:] +
+                           ["--gpus", "1", "--dump-outputs", str(d)], cwd=ROOT, env=_env(), capture_output=True,
+                           text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        j = _json_line(r.stdout)
+        assert j["steps"] == steps and j["warmup"] == 0 and j["ms_per_step"] > 0 and j["value"] > 0
+        assert j["value"] == pytest.approx(2 * 2 * 128 / (j["ms_per_step"] / 1000), rel=1e-3)
+        for k in ("value_bf16", "value_fp32_weights", "notebook_sweep", "same_node_reference_path", "box_calibration",
+                  "transports", "p2p"):
+            assert k not in j, k
+        assert sorted(os.listdir(d)) == ["window_nll.npy"]
+        outs.append((j, np.load(d / "window_nll.npy")))
+    (j0, a0), (_, a1), (_, a3) = outs
+    assert a0.dtype in (np.float32, np.float64) and a0.shape == (2, 2) and np.isfinite(a0).all()
+    assert np.array_equal(a0, a1)
+    # one timed step from a cold start covers windows 0-3: the reported PPL is the token-weighted mean of the dump
+    from llm_inference_in_distributed_edge_networks_amd.eval.windows import sliding_windows
+    w = np.array([x.weight for x in sliding_windows(299_078, 128, 32)[:4]], dtype=np.float64).reshape(2, 2)
+    assert j0["ppl_random_weights"] == pytest.approx(float(np.exp((a0.astype(np.float64) * w).sum() / w.sum())),
+                                                     rel=1e-9)
+    # the third of three steps works on other windows than the first
+    assert a3.shape == (2, 2) and not np.array_equal(a3, a0)
+
+
 def _check_deep(d, n):
     assert d[f"value_pp{n}"] > 0, d.get(f"pp{n}")
     deep = d[f"pp{n}"]
@@ -105,9 +138,10 @@ def _check_deep(d, n):
 @pytest.mark.parametrize("pp", [4, 8])
 def test_bench_deep_pipeline_cpu(pp):
     """BASELINE configs 4-5 as real pp-stage pipelines (--pp), gloo ranks on CPU."""
-    r = _torchrun(pp, BENCH[:-2] + ["--gpus", str(pp), "--pp", str(pp), "--model", "tiny-qwen2"]
+    r = _torchrun(pp, BENCH[:-2] + ["--gpus", str(pp), "--pp", str(pp), "--model", "tiny-qwen2", "--full"]
                   if pp <= 4 else ["bench.py", "--model", "byte-qwen2", "--batch", "1", "--microbatches", "2",
-                                   "--steps", "1", "--warmup", "1", "--max-length", "64", "--gpus", "8", "--pp", "8"],
+                                   "--steps", "1", "--warmup", "1", "--max-length", "64", "--gpus", "8", "--pp", "8",
+                                   "--full"],
                   timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     d = _json_line(r.stdout)
@@ -119,7 +153,7 @@ def test_bench_eight_ranks_reports_pp8_cpu():
     """The driver's default 8-GPU run (pp2 x dp4 headline) also times one 8-stage pipeline (BASELINE config 5's
     shape) and reports it beside the headline."""
     r = _torchrun(8, ["bench.py", "--model", "byte-qwen2", "--batch", "1", "--steps", "2", "--warmup", "1",
-                      "--max-length", "64", "--split", "3", "--gpus", "8"], timeout=900)
+                      "--max-length", "64", "--split", "3", "--gpus", "8", "--full"], timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     d = _json_line(r.stdout)
     assert d["config"]["parallelism"] == "pp2xdp4" and d["n_gpus"] == 8
@@ -167,15 +201,16 @@ def test_bench_self_launch_equals_local():
     reports them; its PPL equals the single-process run over the same windows (--microbatches doubled at N=1:
     both process batches 0..2m-1 of the pool per step)."""
     base = BENCH[:4] + BENCH[6:]          # without "--microbatches 2"
-    r4 = subprocess.run([sys.executable] + base + ["--microbatches", "2", "--gpus", "4", "--pp", "2"], cwd=ROOT,
+    r4 = subprocess.run([sys.executable] + base + ["--microbatches", "2", "--gpus", "4", "--pp", "2", "--full"],
+                        cwd=ROOT,
                         env=_env(), capture_output=True, text=True, timeout=600)
     assert r4.returncode == 0, r4.stderr[-3000:]
     d4 = _json_line(r4.stdout)
     assert d4["n_gpus"] == 4 and d4["world_size"] == 4 and d4["launch"] == "self" and d4["backend"] == "gloo"
     assert [x["rank"] for x in d4["rank_devices"]] == [0, 1, 2, 3]
     assert d4["config"]["parallelism"] == "pp2xdp2"
-    r1 = subprocess.run([sys.executable] + base + ["--microbatches", "4", "--gpus", "1"], cwd=ROOT, env=_env(),
-                        capture_output=True, text=True, timeout=600)
+    r1 = subprocess.run([sys.executable] + base + ["--microbatches", "4", "--gpus", "1", "--full"], cwd=ROOT,
+                        env=_env(), capture_output=True, text=True, timeout=600)
     assert r1.returncode == 0, r1.stderr[-3000:]
     d1 = _json_line(r1.stdout)
     assert d1["launch"] == "single" and d1["config"]["global_batch"] == d4["config"]["global_batch"]
@@ -193,8 +228,8 @@ def test_bench_failed_rank_exits_nonzero_without_json(rank):
     """A rank that dies (here on purpose, after its measurement) must leave the self-launching parent with a
     non-zero exit code and NO JSON line: rank 0 reports only after every rank passed the final barrier."""
     env = dict(_env(), EDGE_BENCH_FAIL_RANK=str(rank), EDGE_TUNING="1")   # a tuning-mode-only test hook
-    r = subprocess.run([sys.executable] + BENCH + ["--gpus", "2"], cwd=ROOT, env=env, capture_output=True, text=True,
-                       timeout=600)
+    r = subprocess.run([sys.executable] + BENCH + ["--gpus", "2", "--full"], cwd=ROOT, env=env, capture_output=True,
+                       text=True, timeout=600)
     assert r.returncode != 0
     assert not [l for l in r.stdout.splitlines() if l.startswith("{")], r.stdout
     assert "fails on purpose" in r.stderr
@@ -226,8 +261,8 @@ def test_bench_secondary_failure_keeps_headline(hook, rc):
     env = dict(_env(), EDGE_TUNING="1", **{k: v})
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2",
                         "--master-addr", "127.0.0.1", "--master-port", str(_port())] + BENCH +
-                       ["--gpus", "2", "--deep-pp-timeout", "10"], cwd=ROOT, env=env, capture_output=True, text=True,
-                       timeout=300)
+                       ["--gpus", "2", "--full", "--deep-pp-timeout", "10"], cwd=ROOT, env=env, capture_output=True,
+                       text=True, timeout=300)
     assert r.returncode == rc, r.stderr[-3000:]
     d = _json_line(r.stdout)
     assert d["value"] > 0 and d["ppl_random_weights"] > 1

@@ -25,9 +25,10 @@ def _port():
 
 
 def _run(n, extra=(), env_extra=None, self_launch=False, full=False):
-    """bench.py on ``n`` ranks sharing cuda:0.  Without ``full`` the N = 1 extras (notebook-sweep timing, HF-eager
-    comparison) and the N > 1 transports record are skipped: each test then stays well under a minute."""
+    """``bench.py --full`` on ``n`` ranks sharing cuda:0.  Without ``full`` the N = 1 extras (notebook-sweep timing,
+    HF-eager comparison) and the N > 1 transports record are skipped: each test then stays well under a minute."""
     env = dict(os.environ, EDGE_SHARED_GPU="1", **(env_extra or {}))
+    extra = list(extra) + ["--full"]
     if not full:
         extra = list(extra) + ["--no-sweep", "--no-hf-compare"] + (["--no-transports"] if n > 1 else [])
     if n == 1 or self_launch:
@@ -55,6 +56,30 @@ def test_two_ranks_one_gpu_equals_single_process():
     assert "notebook_sweep" in one and one["notebook_sweep"]["windows_per_s"] > 0
     chk = _run(2, ["--no-graphs"], {"EDGE_P2P_CHECK": "1"})
     assert chk["ppl_random_weights"] == pytest.approx(one["ppl_random_weights"], rel=1e-9)
+
+
+def test_plain_run_dumps_last_step_outputs(tmp_path):
+    """``bench.py`` without ``--full`` on the HIP-graph path: the headline only, and ``--dump-outputs`` holds the last
+    timed step's per-window NLL of every micro-batch (copies: the captured graph reuses its output buffer), whose
+    token-weighted mean is the reported PPL when one step is timed."""
+    import numpy as np
+    from llm_inference_in_distributed_edge_networks_amd.eval.windows import sliding_windows
+    cmd = ([sys.executable] + ARGS[:7] + ["--steps", "1", "--warmup", "1"] + ARGS[11:] +
+           ["--dump-outputs", str(tmp_path)])
+    r = subprocess.run(cmd, cwd=ROOT, env=dict(os.environ), capture_output=True, text=True, timeout=240)
+    assert r.returncode == 0, r.stderr[-3000:]
+    j = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    assert j["steps"] == 1 and j["config"]["hip_graphs"] is True and j["ms_per_step"] > 0
+    for k in ("value_bf16", "value_fp32_weights", "notebook_sweep", "same_node_reference_path", "box_calibration"):
+        assert k not in j, k
+    assert sorted(os.listdir(tmp_path)) == ["window_nll.npy"]
+    a = np.load(tmp_path / "window_nll.npy")
+    assert a.dtype in (np.float32, np.float64) and a.shape == (2, 4) and np.isfinite(a).all()
+    assert not np.array_equal(a[0], a[1])
+    # the timed step follows one warmup step of 2 micro-batches x 4 windows: it covers windows 8-15
+    w = np.array([x.weight for x in sliding_windows(299_078, 256, 32)[8:16]], dtype=np.float64).reshape(2, 4)
+    assert j["ppl_random_weights"] == pytest.approx(math.exp(float((a.astype(np.float64) * w).sum() / w.sum())),
+                                                    rel=1e-9)
 
 
 def test_self_launch_one_gpu_equals_single_process():
