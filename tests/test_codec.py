@@ -160,6 +160,51 @@ def test_top_rho_k(mass, exp):
     assert int(C.wire.top_rho_k(imp, mass)) == exp
 
 
+def test_dyadic_importance_k_is_exact():
+    """The generator behind the GPU byte comparisons of variable-k messages (test_kvar_gpu.py): on its windows the
+    top-rho cut is the same from fp64 sequential sums, an fp32 running sum and fp32 sums in a random order; every
+    case has a window with k = 0, every case at ratio >= 0.5 one with k = S - 1, and every codec whose lo row is no
+    multiple of 16 bytes meets a hi section that needs the 16-byte round-up."""
+    import helpers as T
+    assert sorted(T.KVAR_CODECS) == sorted(n for n, s in W.CODECS.items() if s.uses_ratio)
+    unaligned = {}
+    for B, S, H in T.KVAR_SHAPES:
+        imp = T.dyadic_importance(B, S, T.kvar_seed(B, S))
+        assert imp.dtype == torch.float32 and imp.shape == (B, S)
+        assert torch.equal(imp * 65536, torch.round(imp * 65536)) and float(imp.sum(1).max()) < 4
+        assert bool((imp == 0).all(0).any())                                     # an all-zero column
+        assert all(torch.equal(imp[:, c], imp[:, c + 1]) for c in range(0, S - 1, 7))
+        desc = torch.sort(imp, dim=1, stable=True).values.flip(1)
+        cs32 = torch.cumsum(desc, 1)
+        assert torch.equal(cs32.double(), torch.cumsum(desc.double(), 1))        # every partial sum exact in fp32
+        # exclusive mass of position i from the i largest terms summed in a random order (fp32, sequential)
+        pm = torch.Generator().manual_seed(S)
+        low = torch.tril(torch.ones(S, S), -1)                                   # [i, j] = 1 for j < i
+        excl_perm = torch.stack([(low * desc[b])[:, torch.randperm(S, generator=pm)].cumsum(1)[:, -1]
+                                 for b in range(B)])
+        for ratio in T.KVAR_RATIOS:
+            mass = 1.0 - ratio
+            ks = W.top_rho_k(imp, mass)
+            for excl in (cs32 - desc, excl_perm):
+                ge = excl >= torch.tensor(mass, dtype=torch.float32)
+                keep = torch.where(ge.any(1), ge.to(torch.int64).argmax(1), torch.full((B,), S))
+                assert torch.equal(S - keep, ks), (B, S, ratio)
+            assert int(ks[0]) == 0 and bool(((ks > 0) & (ks < S - 1)).any()), ks    # k = 0 and interior values
+            if ratio >= 0.5:
+                assert int(ks[1]) == S - 1
+            for name in T.KVAR_CODECS:
+                spec = T.kvar_spec(name, H)
+                L = W.layout(spec, B, S, H, -1, torch.float32, kvar=True)
+                rb = L.row_bytes(L.lo_fmt)
+                if rb % 16:
+                    unaligned.setdefault(name, []).append(int(ks.sum()) * rb % 16)
+                msg, _ = W.encode(T.kvar_activations(B, S, H, 1), spec, B, S, ratio, imp, selection="top_rho")
+                assert W.message_k(msg, L).tolist() == ks.tolist()
+                assert torch.isfinite(W.decode(msg, spec, L, torch.float32)).all()
+    assert sorted(unaligned) == ["mixed_mxfp4_mxfp8", "mixed_rgroup_int8", "mxfp4_keep"]
+    assert all(any(r for r in v) for v in unaligned.values()), unaligned
+
+
 @pytest.mark.parametrize("codec", ["ref_int4_global", "mixed_int4_int8", "int8_token_keep"])
 def test_top_rho_message_roundtrip(codec):
     B, S, H = 3, 64, 128
