@@ -17,12 +17,23 @@
 // its un-selected tokens in fp32, Experiments/Qwen2-0.5B/qwen_layer_wise.py:54-70).
 #include "common.h"
 
-enum { FMT_BF16 = 0, FMT_INT8 = 1, FMT_INT4 = 2, FMT_INT2 = 3, FMT_F32 = 4, FMT_MXFP4 = 5, FMT_MXFP8 = 6, FMT_GRP = 7 };
+enum { FMT_BF16 = 0, FMT_INT8 = 1, FMT_INT4 = 2, FMT_INT2 = 3, FMT_F32 = 4, FMT_MXFP4 = 5, FMT_MXFP8 = 6, FMT_GRP = 7,
+       FMT_GRPR = 8 };
 // Head-group rows (FMT_GRP): every 64-channel group g (one head's width) has its own bit width b_g in {2, 3, 4, 5, 6, 8}
 // (the plan: one byte per group in the message at off_plan, chosen from the boundary's channel-group sensitivity) and
 // its own max-abs scale s = max|x| / qmax_b (qmax = 2^(b-1) - 1: 1 / 3 / 7 / 15 / 31 / 127): row = [group 0 codes
 // (8 b_0 bytes)] ... [group G-1 codes][G fp32 scales]; the group's 64 two's-complement b-bit codes form one
 // little-endian bit stream (code c at bits [b c, b c + b)), so 8 consecutive codes are b whole bytes.
+// Rotated head-group rows (FMT_GRPR): the bytes of FMT_GRP rows (same plan, same row size), but the codes and the scale
+// of a group describe y = H64 x / 8 with H64 the 64 x 64 Sylvester / Walsh-Hadamard +-1 matrix (H64 / 8 orthonormal and
+// symmetric, so its own inverse; QuaRot / SpinQuant): a massive channel's energy spreads over its group, max|y| - and
+// with it the step - falls by up to 8.  Encode: butterflies (a, b) -> (a + b, a - b) in fp32 at channel strides 1, 2,
+// 4, 8, 16, 32 in that order, times 0.125f (exact), then exactly FMT_GRP's quantizer.  Decode: the same butterflies
+// on the integer codes (exact, |sum| <= 64 * 127), then x' = float(sum) * (s * 0.125f) - one rounding per factor, no
+// add after a multiply anywhere, so nothing for fp contraction to fuse and the CPU oracle (codec/wire.py) agrees bit
+// for bit.  Messages with rows of this format run the ROT instantiations of pack_kernel / unpack_kernel
+// (pack_kernel<NCH, T, true>, every rotated branch under `if constexpr (ROT)`), so the instantiations every other
+// codec runs keep their instruction stream.
 // OCP microscaling rows (FMT_MXFP4: E2M1 codes, FMT_MXFP8: E4M3 codes): blocks of 32 consecutive channels share one
 // E8M0 scale 2^(floor(log2 max|x|) - emax) (emax 2 / 8), stored after the row's codes: [codes][H/32 scale bytes].
 // Quantize / dequantize with gfx950's scaled converts (v_cvt_scalef32_pk_fp4_f32 / _fp8_f32 and the inverses:
@@ -37,14 +48,18 @@ struct CodecArgs {
   long long off_plan;           // >= 0: FMT_GRP bit plan (one byte per 64-channel group)
   int B, S, H, k, mw;           // mw: mask words per window
   int hi_fmt, lo_fmt, scale_mode, qmax_hi, qmax_lo, ch_kind;
-  int grp_code_bytes;           // FMT_GRP: sum over groups of 8 b_g (row = codes + 4 G scale bytes)
+  int grp_code_bytes;           // FMT_GRP / FMT_GRPR: sum over groups of 8 b_g (row = codes + 4 G scale bytes)
 };
 
 __device__ __forceinline__ int fmt_row_bytes(int fmt, int H) {
   return fmt == FMT_F32 ? 4 * H : fmt == FMT_BF16 ? 2 * H : fmt == FMT_INT8 ? H : fmt == FMT_INT4 ? H / 2 :
          fmt == FMT_MXFP4 ? H / 2 + H / 32 : fmt == FMT_MXFP8 ? H + H / 32 : H / 4;
 }
+template <bool ROT>
 __device__ __forceinline__ int row_bytes(const CodecArgs& a, int fmt) {
+  if constexpr (ROT) {
+    if (fmt == FMT_GRPR) return a.grp_code_bytes + 4 * (a.H / 64);
+  }
   return fmt == FMT_GRP ? a.grp_code_bytes + 4 * (a.H / 64) : fmt_row_bytes(fmt, a.H);
 }
 
@@ -392,7 +407,83 @@ __device__ __forceinline__ void grp_unpack8(const uint8_t* __restrict__ row, con
   }
 }
 
-template <int NCH, class T>
+// FMT_GRPR: the unnormalised 64-point Walsh-Hadamard transform of a group held 8 consecutive channels per lane by the
+// 8 lanes sharing lane >> 3.  Channel strides 1, 2, 4 pair values of one lane (wht8), strides 8, 16, 32 pair lanes
+// lane ^ 1, 2, 4 (wht_lanes): the lane with the bit clear holds a and keeps a + b, its partner holds b and keeps a - b.
+// Every lane of a group must be here: H % 64 == 0 makes the col >= H early-out drop whole groups and a row's format
+// is wave-uniform (what grp_pack8's max-abs shuffles rely on too).
+template <class V>
+__device__ __forceinline__ void wht8(V (&v)[8]) {
+#pragma unroll
+  for (int h = 1; h < 8; h <<= 1)
+#pragma unroll
+    for (int e = 0; e < 8; ++e)
+      if (!(e & h)) {
+        const V x = v[e], y = v[e + h];
+        v[e] = x + y;
+        v[e + h] = x - y;
+      }
+}
+template <class V>
+__device__ __forceinline__ void wht_lanes(V (&v)[8]) {
+  const int lane = threadIdx.x & 63;
+#pragma unroll
+  for (int m = 1; m < 8; m <<= 1) {
+    const bool up = lane & m;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const V o = __shfl_xor(v[e], m, 64);
+      v[e] = up ? o - v[e] : v[e] + o;
+    }
+  }
+}
+__device__ __forceinline__ void grp_pack8_rot(uint8_t* __restrict__ row, const CodecArgs& a, int col,
+                                              const float (&v)[8]) {
+  float y[8];
+#pragma unroll
+  for (int e = 0; e < 8; ++e) y[e] = v[e];
+  wht8(y);
+  wht_lanes(y);
+#pragma unroll
+  for (int e = 0; e < 8; ++e) y[e] *= 0.125f;
+  grp_pack8(row, a, col, y);
+}
+// As grp_unpack8 (NaN from the first bad group on), but `bad` - uniform over the group's 8 lanes - only zeroes the
+// codes before the shuffles and is applied after them, so no lane of a group leaves early.
+__device__ __forceinline__ void grp_unpack8_rot(const uint8_t* __restrict__ row, const CodecArgs& a, int col,
+                                                float (&o)[8]) {
+  const int lane = threadIdx.x & 63;
+  const uint8_t* plan = a.msg + a.off_plan;
+  const int g = col >> 6;
+  const int sub = lane & 7;
+  int off = 0;
+  bool bad = false;
+  for (int i = 0; i < g; ++i) {
+    const int b = plan[i];
+    bad |= !grp_bits_ok(b);
+    off += grp_bits_ok(b) ? 8 * b : 0;
+  }
+  const int bits = plan[g];
+  bad |= !grp_bits_ok(bits) || off + 8 * bits > a.grp_code_bytes;
+  int q[8];
+  float s = 0.f;
+  if (bad) {
+#pragma unroll
+    for (int e = 0; e < 8; ++e) q[e] = 0;
+  } else {
+    const uint64_t w = grp_load(row + off + sub * bits, bits);
+    s = *(const float*)(row + a.grp_code_bytes + 4 * g);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) q[e] = ((int)((uint32_t)(w >> (bits * e)) << (32 - bits))) >> (32 - bits);
+  }
+  wht8(q);
+  wht_lanes(q);
+  const float sc = s * 0.125f;
+#pragma unroll
+  for (int e = 0; e < 8; ++e) o[e] = bad ? __builtin_nanf("") : (float)q[e] * sc;
+}
+
+template <int NCH, class T, bool ROT = false>
 __global__ __launch_bounds__(256) void pack_kernel(CodecArgs a) {
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= a.B * a.S) return;
@@ -403,12 +494,12 @@ __global__ __launch_bounds__(256) void pack_kernel(CodecArgs a) {
   const int slot_lo = lo_prefix(mask, a.mw, j, is_lo);
   const int fmt = is_lo ? a.lo_fmt : a.hi_fmt;
   const int qmax = is_lo ? a.qmax_lo : a.qmax_hi;
-  const int rb = row_bytes(a, fmt);
+  const int rb = row_bytes<ROT>(a, fmt);
   uint8_t* dst;
   if (a.off_kvec >= 0) {
     int Kb, Kt;
     kvar_prefix(a, b, Kb, Kt);
-    const long long off_hi = a.off_lo + (((long long)Kt * row_bytes(a, a.lo_fmt) + 15) & ~15ll);
+    const long long off_hi = a.off_lo + (((long long)Kt * row_bytes<ROT>(a, a.lo_fmt) + 15) & ~15ll);
     dst = is_lo ? a.msg + a.off_lo + ((size_t)Kb + slot_lo) * rb
                 : a.msg + off_hi + ((size_t)b * a.S - Kb + (j - slot_lo)) * rb;
   } else {
@@ -421,7 +512,8 @@ __global__ __launch_bounds__(256) void pack_kernel(CodecArgs a) {
 
   // scale / quantiser for this row
   float inv = 0.f, mul = 0.f;  // code = round(x * inv) for token & channel; window mode uses ref formula
-  const bool raw = fmt == FMT_BF16 || fmt == FMT_F32 || fmt == FMT_MXFP4 || fmt == FMT_MXFP8 || fmt == FMT_GRP;
+  bool raw = fmt == FMT_BF16 || fmt == FMT_F32 || fmt == FMT_MXFP4 || fmt == FMT_MXFP8 || fmt == FMT_GRP;
+  if constexpr (ROT) raw |= fmt == FMT_GRPR;
   if (raw && a.scale_mode == SC_TOKEN && lane == 0) scales[row] = 0.f;
   if (!raw) {
     if (a.scale_mode == SC_TOKEN) {
@@ -457,6 +549,12 @@ __global__ __launch_bounds__(256) void pack_kernel(CodecArgs a) {
     if (fmt == FMT_GRP) {
       grp_pack8(dst, a, col, v[c]);
       continue;
+    }
+    if constexpr (ROT) {
+      if (fmt == FMT_GRPR) {
+        grp_pack8_rot(dst, a, col, v[c]);
+        continue;
+      }
     }
     if (fmt == FMT_BF16) {
       u32x4_t w;
@@ -514,7 +612,7 @@ __device__ __forceinline__ void store8(float* dst, const float (&o)[8]) {
   *(f32x4_t*)(dst + 4) = f32x4_t{o[4], o[5], o[6], o[7]};
 }
 
-template <int NCH, class T>
+template <int NCH, class T, bool ROT = false>
 __global__ __launch_bounds__(256) void unpack_kernel(CodecArgs a) {
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= a.B * a.S) return;
@@ -525,12 +623,12 @@ __global__ __launch_bounds__(256) void unpack_kernel(CodecArgs a) {
   const int slot_lo = lo_prefix(mask, a.mw, j, is_lo);
   const int fmt = is_lo ? a.lo_fmt : a.hi_fmt;
   const int qmax = is_lo ? a.qmax_lo : a.qmax_hi;
-  const int rb = row_bytes(a, fmt);
+  const int rb = row_bytes<ROT>(a, fmt);
   const uint8_t* src;
   if (a.off_kvec >= 0) {
     int Kb, Kt;
     kvar_prefix(a, b, Kb, Kt);
-    const long long off_hi = a.off_lo + (((long long)Kt * row_bytes(a, a.lo_fmt) + 15) & ~15ll);
+    const long long off_hi = a.off_lo + (((long long)Kt * row_bytes<ROT>(a, a.lo_fmt) + 15) & ~15ll);
     src = is_lo ? a.msg + a.off_lo + ((size_t)Kb + slot_lo) * rb
                 : a.msg + off_hi + ((size_t)b * a.S - Kb + (j - slot_lo)) * rb;
   } else {
@@ -539,7 +637,8 @@ __global__ __launch_bounds__(256) void unpack_kernel(CodecArgs a) {
   }
   const float* scales = (const float*)(a.msg + a.off_scale);
   float s = 0.f;
-  if (fmt != FMT_BF16 && fmt != FMT_F32 && fmt != FMT_MXFP4 && fmt != FMT_MXFP8 && fmt != FMT_GRP) {
+  if (fmt != FMT_BF16 && fmt != FMT_F32 && fmt != FMT_MXFP4 && fmt != FMT_MXFP8 && fmt != FMT_GRP &&
+      !(ROT && fmt == FMT_GRPR)) {
     if (a.scale_mode == SC_TOKEN) s = scales[row];
     else if (a.scale_mode == SC_WINDOW) s = scales[b];
   }
@@ -573,6 +672,14 @@ __global__ __launch_bounds__(256) void unpack_kernel(CodecArgs a) {
       grp_unpack8(src, a, col, o);
       store8(out + col, o);
       continue;
+    }
+    if constexpr (ROT) {
+      if (fmt == FMT_GRPR) {
+        float o[8];
+        grp_unpack8_rot(src, a, col, o);
+        store8(out + col, o);
+        continue;
+      }
     }
     int q[8];
     if (fmt == FMT_INT8) {
@@ -683,19 +790,26 @@ EDGE_API int edge_rowmax(const float* in, float* out, int R, int H, hipStream_t 
   return (int)hipGetLastError();
 }
 
-// grp_code_bytes: FMT_GRP rows' code bytes (sum 8 b_g over the plan at msg + opl; 0 without FMT_GRP)
+// grp_code_bytes: FMT_GRP / FMT_GRPR rows' code bytes (sum 8 b_g over the plan at msg + opl; 0 without such rows).
+// A message with FMT_GRPR rows goes to the ROT instantiations (which handle every other format too).
+static bool has_fmt(int hi_fmt, int lo_fmt, int fmt) { return hi_fmt == fmt || lo_fmt == fmt; }
+
 EDGE_API int edge_pack(const void* x, void* msg, long long om, long long os, long long oh, long long ol, long long okv,
                        long long opl, int B, int S, int H, int k, int hi_fmt, int lo_fmt, int scale_mode, int qmax_hi,
                        int qmax_lo, int ch_kind, int grp_code_bytes, int x_f32, hipStream_t st) {
   if (H % 32) return (int)hipErrorInvalidValue;
-  if ((hi_fmt == FMT_GRP || lo_fmt == FMT_GRP) && (H % 64 || opl < 0 || grp_code_bytes <= 0))
+  const bool rot = has_fmt(hi_fmt, lo_fmt, FMT_GRPR);
+  if ((rot || has_fmt(hi_fmt, lo_fmt, FMT_GRP)) && (H % 64 || opl < 0 || grp_code_bytes <= 0))
     return (int)hipErrorInvalidValue;
   CodecArgs a = make_args((void*)x, msg, om, os, oh, ol, okv, opl, B, S, H, k, hi_fmt, lo_fmt, scale_mode, qmax_hi,
                           qmax_lo, ch_kind, grp_code_bytes);
   const int rows = B * S;
   if (rows <= 0) return 0;
-  if (x_f32) DISPATCH_NCH(H, hipLaunchKernelGGL((pack_kernel<NCH, float>), dim3((rows + 3) / 4), dim3(256), 0, st, a));
-  else DISPATCH_NCH(H, hipLaunchKernelGGL((pack_kernel<NCH, bf16_t>), dim3((rows + 3) / 4), dim3(256), 0, st, a));
+  const dim3 grid((rows + 3) / 4), block(256);
+  if (rot && x_f32) DISPATCH_NCH(H, hipLaunchKernelGGL((pack_kernel<NCH, float, true>), grid, block, 0, st, a));
+  else if (rot) DISPATCH_NCH(H, hipLaunchKernelGGL((pack_kernel<NCH, bf16_t, true>), grid, block, 0, st, a));
+  else if (x_f32) DISPATCH_NCH(H, hipLaunchKernelGGL((pack_kernel<NCH, float>), grid, block, 0, st, a));
+  else DISPATCH_NCH(H, hipLaunchKernelGGL((pack_kernel<NCH, bf16_t>), grid, block, 0, st, a));
   return (int)hipGetLastError();
 }
 
@@ -704,13 +818,17 @@ EDGE_API int edge_unpack(void* x, const void* msg, long long om, long long os, l
                          int scale_mode, int qmax_hi, int qmax_lo, int ch_kind, int grp_code_bytes, int x_f32,
                          hipStream_t st) {
   if (H % 32) return (int)hipErrorInvalidValue;
-  if ((hi_fmt == FMT_GRP || lo_fmt == FMT_GRP) && (H % 64 || opl < 0 || grp_code_bytes <= 0))
+  const bool rot = has_fmt(hi_fmt, lo_fmt, FMT_GRPR);
+  if ((rot || has_fmt(hi_fmt, lo_fmt, FMT_GRP)) && (H % 64 || opl < 0 || grp_code_bytes <= 0))
     return (int)hipErrorInvalidValue;
   CodecArgs a = make_args(x, (void*)msg, om, os, oh, ol, okv, opl, B, S, H, k, hi_fmt, lo_fmt, scale_mode, qmax_hi,
                           qmax_lo, ch_kind, grp_code_bytes);
   const int rows = B * S;
   if (rows <= 0) return 0;
-  if (x_f32) DISPATCH_NCH(H, hipLaunchKernelGGL((unpack_kernel<NCH, float>), dim3((rows + 3) / 4), dim3(256), 0, st, a));
-  else DISPATCH_NCH(H, hipLaunchKernelGGL((unpack_kernel<NCH, bf16_t>), dim3((rows + 3) / 4), dim3(256), 0, st, a));
+  const dim3 grid((rows + 3) / 4), block(256);
+  if (rot && x_f32) DISPATCH_NCH(H, hipLaunchKernelGGL((unpack_kernel<NCH, float, true>), grid, block, 0, st, a));
+  else if (rot) DISPATCH_NCH(H, hipLaunchKernelGGL((unpack_kernel<NCH, bf16_t, true>), grid, block, 0, st, a));
+  else if (x_f32) DISPATCH_NCH(H, hipLaunchKernelGGL((unpack_kernel<NCH, float>), grid, block, 0, st, a));
+  else DISPATCH_NCH(H, hipLaunchKernelGGL((unpack_kernel<NCH, bf16_t>), grid, block, 0, st, a));
   return (int)hipGetLastError();
 }

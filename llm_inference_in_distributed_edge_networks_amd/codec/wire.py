@@ -36,7 +36,9 @@ from ..ops._native import call, ptr, stream
 MAGIC = 0x45444742
 VERSION = 1
 FMT_BF16, FMT_INT8, FMT_INT4, FMT_INT2, FMT_F32, FMT_MXFP4, FMT_MXFP8, FMT_GRP = 0, 1, 2, 3, 4, 5, 6, 7
+FMT_GRPR = 8                # FMT_GRP bytes whose codes and scales describe the Hadamard-rotated group
 MX_FORMATS = (FMT_MXFP4, FMT_MXFP8)
+GRP_FORMATS = (FMT_GRP, FMT_GRPR)
 SC_TOKEN, SC_WINDOW, SC_CHANNEL, SC_NONE = 0, 1, 2, 3
 CH_MAXABS, CH_MEAN = 0, 1
 NATIVE = -1  # "keep in the activation dtype" (bf16 on GPU, fp32 in the CPU reference mode)
@@ -54,7 +56,7 @@ class CodecSpec:
     ch_kind: int = CH_MAXABS
     uses_ratio: bool = True      # lo class = int(ratio*S) least important tokens
     needs_importance: bool = True
-    plan: tuple | None = None    # FMT_GRP rows: bits (GROUP_BITS) of every 64-channel group (with_plan)
+    plan: tuple | None = None    # FMT_GRP / FMT_GRPR rows: bits (GROUP_BITS) of every 64-channel group (with_plan)
 
 
 CODECS = {c.name: c for c in [
@@ -78,13 +80,19 @@ CODECS = {c.name: c for c in [
     # the widths come from the relevance of the boundary's channel groups (group_bits / allocate_group_bits)
     CodecSpec("rgroup", 15, FMT_GRP, FMT_GRP, SC_NONE, uses_ratio=False, needs_importance=False),
     CodecSpec("mixed_rgroup_int8", 16, FMT_INT8, FMT_GRP, SC_TOKEN, 127, 0),
+    # rotated head-group rows (FMT_GRPR): rgroup's bytes, but every group is quantized in the basis of the orthonormal
+    # 64-point Walsh-Hadamard transform y = H64 x / 8 (QuaRot / SpinQuant), which spreads a massive channel over its
+    # group: max|y| falls by up to 8 and with it the step.  Pays from 4 bits up; at 2 - 3 bits plain rgroup's error on
+    # such a group is bounded by the small channels it zeroes and rotation can lose.  The plan allocator is fed the
+    # UNROTATED sensitivity / relevance tables: a table for rotated groups needs max_c |(H x)_c|^2 in the LRP engine.
+    CodecSpec("rgroup_rot", 17, FMT_GRPR, FMT_GRPR, SC_NONE, uses_ratio=False, needs_importance=False),
 ]}
-GROUP = 64                  # channels per group of FMT_GRP rows
+GROUP = 64                  # channels per group of FMT_GRP / FMT_GRPR rows
 GROUP_BITS = (2, 3, 4, 5, 6, 8)
 
 
 def needs_plan(spec: CodecSpec) -> bool:
-    return FMT_GRP in (spec.hi_fmt, spec.lo_fmt)
+    return spec.hi_fmt in GRP_FORMATS or spec.lo_fmt in GRP_FORMATS
 
 
 def with_plan(spec: CodecSpec, plan) -> CodecSpec:
@@ -206,7 +214,7 @@ def _a16(n: int) -> int:
 
 
 def _row_bytes(fmt: int, H: int, plan=None) -> int:
-    if fmt == FMT_GRP:   # codes of every group (8 * bits bytes), then one fp32 scale per group
+    if fmt in GRP_FORMATS:   # codes of every group (8 * bits bytes), then one fp32 scale per group
         return sum(8 * b for b in plan) + 4 * len(plan)
     return {FMT_BF16: 2 * H, FMT_INT8: H, FMT_INT4: H // 2, FMT_INT2: H // 4, FMT_F32: 4 * H,
             FMT_MXFP4: H // 2 + H // 32, FMT_MXFP8: H + H // 32}[fmt]
@@ -228,7 +236,7 @@ class Layout:
     total: int        # bytes of the message buffer (the capacity when kvar)
     kvar: bool = False
     off_kvec: int = -1
-    plan: tuple | None = None   # FMT_GRP group bits (also stored in the message at off_plan, one byte each)
+    plan: tuple | None = None   # FMT_GRP / FMT_GRPR group bits (also stored in the message at off_plan, one byte each)
     off_plan: int = -1
 
     def row_bytes(self, fmt: int) -> int:
@@ -273,7 +281,7 @@ def layout(spec: CodecSpec, B: int, S: int, H: int, k: int, dtype: torch.dtype =
     hi = nf if spec.hi_fmt == NATIVE else spec.hi_fmt
     lo = nf if spec.lo_fmt == NATIVE else spec.lo_fmt
     plan = None
-    if FMT_GRP in (hi, lo):
+    if hi in GRP_FORMATS or lo in GRP_FORMATS:
         if H % GROUP:
             raise ValueError(f"head-group rows need a hidden size multiple of {GROUP}")
         plan = spec.plan if spec.plan is not None else (4,) * (H // GROUP)
@@ -487,11 +495,32 @@ def _grp_bits_unpack(b: torch.Tensor, bits: int) -> torch.Tensor:
     return c.reshape(n, 64).float()
 
 
-def _grp_pack(rows: torch.Tensor, plan) -> torch.Tensor:
+def _wht64(v: torch.Tensor) -> torch.Tensor:
+    """Unnormalised 64-point Walsh-Hadamard transform (Sylvester order) of the last dimension: the butterflies
+    (a, b) -> (a + b, a - b) at channel strides 1, 2, 4, 8, 16, 32 in that order, in the tensor's own arithmetic
+    (fp32 adds on encode, integer adds on decode) - the order and operations of csrc/codec.hip wht8 / wht_lanes."""
+    lead = v.shape[:-1]
+    for h in (1, 2, 4, 8, 16, 32):
+        p = v.reshape(*lead, GROUP // (2 * h), 2, h)
+        a, b = p[..., 0, :], p[..., 1, :]
+        v = torch.stack((a + b, a - b), -2).reshape(*lead, GROUP)
+    return v
+
+
+def hadamard64(x: torch.Tensor) -> torch.Tensor:
+    """y_g = H64 x_g / 8 for every 64-channel group of fp32 rows [n, H]: orthonormal, symmetric, its own inverse.
+    The scaling by 1/8 is exact, so the only roundings are those of the 6 butterfly levels' fp32 adds."""
+    n, H = x.shape
+    return (_wht64(x.float().reshape(n, H // GROUP, GROUP)) * 0.125).reshape(n, H)
+
+
+def _grp_pack(rows: torch.Tensor, plan, rot: bool = False) -> torch.Tensor:
     """FMT_GRP rows: per 64-channel group g of b_g bits, s = max|x| / qmax_b (qmax = 2^(b-1) - 1), codes
     clamp(round(x * (1 / s)), -qmax, qmax) packed as a b-bit stream (csrc/codec.hip grp_pack8); then the G fp32
-    scales."""
+    scales.  ``rot`` (FMT_GRPR): the same of the rotated groups ``hadamard64(rows)``."""
     n, H = rows.shape
+    if rot:
+        rows = hadamard64(rows)
     parts, scales = [], []
     for g, b in enumerate(plan):
         blk = rows[:, g * GROUP:(g + 1) * GROUP].float()
@@ -519,6 +548,27 @@ def _grp_unpack(b: torch.Tensor, plan, n: int, H: int) -> torch.Tensor:
     return torch.cat(out, 1)
 
 
+def _grpr_unpack(b: torch.Tensor, msg_plan, plan, n: int, H: int) -> torch.Tensor:
+    """FMT_GRPR rows -> fp32 [n, H]: the group's integer codes go through the butterflies as integers (exact) and one
+    multiply by s / 8 gives x' = H64 q s / 8 (csrc/codec.hip grp_unpack8_rot).  The row stride comes from the codec's
+    plan, the widths from the MESSAGE's plan bytes as on the GPU: a width outside GROUP_BITS, or a group stream
+    reaching past the row's code bytes, gives NaN from that group on (invalid widths count 0 bytes in the offset)."""
+    r = b.reshape(n, _row_bytes(FMT_GRPR, H, plan))
+    cb = sum(8 * x for x in plan)
+    sc = r[:, cb:].contiguous().view(torch.float32).reshape(n, len(plan))
+    out, off, bad = [], 0, False
+    for g, bits in enumerate(msg_plan):
+        ok = bits in GROUP_BITS
+        bad = bad or not ok or off + 8 * bits > cb
+        if bad:
+            out.append(torch.full((n, GROUP), float("nan")))
+        else:
+            q = _grp_bits_unpack(r[:, off:off + 8 * bits].contiguous(), bits).to(torch.int64)
+            out.append(_wht64(q).float() * (sc[:, g:g + 1] * 0.125))
+        off += 8 * bits if ok else 0
+    return torch.cat(out, 1)
+
+
 def _header(spec: CodecSpec, L: Layout) -> torch.Tensor:
     return torch.tensor([MAGIC, VERSION, spec.cid, L.B, L.S, L.H, -1 if L.kvar else L.k, L.hi_fmt], dtype=torch.int32)
 
@@ -542,7 +592,7 @@ def _encode_cpu(x, spec, L, lo_mask):
     if spec.scale_mode == SC_TOKEN:
         scales = torch.zeros(B, S)
         for is_lo, fmt, qmax in ((False, L.hi_fmt, spec.qmax_hi), (True, L.lo_fmt, spec.qmax_lo)):
-            if fmt in (FMT_BF16, FMT_F32, FMT_GRP) or fmt in MX_FORMATS:
+            if fmt in (FMT_BF16, FMT_F32) or fmt in GRP_FORMATS or fmt in MX_FORMATS:
                 continue
             sel = lo_mask if is_lo else ~lo_mask
             am = xf.abs().amax(-1)
@@ -571,6 +621,8 @@ def _encode_cpu(x, spec, L, lo_mask):
             data = _mx_pack(rows, fmt)
         elif fmt == FMT_GRP:
             data = _grp_pack(rows, L.plan)
+        elif fmt == FMT_GRPR:
+            data = _grp_pack(rows, L.plan, rot=True)
         else:
             if spec.scale_mode == SC_TOKEN:
                 srow = scales[sel]
@@ -617,6 +669,8 @@ def _decode_cpu(msg, spec, L, dtype):
             rows = _mx_unpack(raw, fmt, n, H)
         elif fmt == FMT_GRP:
             rows = _grp_unpack(raw, L.plan, n, H)
+        elif fmt == FMT_GRPR:
+            rows = _grpr_unpack(raw, msg[L.off_plan:L.off_plan + len(L.plan)].tolist(), L.plan, n, H)
         else:
             q = _unpack_rows(raw, fmt, n, H)
             if spec.scale_mode == SC_TOKEN:

@@ -42,7 +42,7 @@ class Params:
     split_layers: list = field(default_factory=list)   # explicit stage boundaries (last layer of each stage but the last)
     head_weights: str = ""                   # path to attention_head_weights.json (weighted_importance)
     selection: str = "ratio"                 # "ratio" (int(ratio*S) least important) | "top_rho" (mass 1 - ratio kept)
-    group_relevance: str = ""                # channel_group_relevance.json (head-group codecs rgroup / mixed_rgroup_int8)
+    group_relevance: str = ""                # channel_group_relevance.json (head-group codecs rgroup / rgroup_rot / mixed_rgroup_int8)
     group_avg_bits: float = 4.0              # head-group codecs: average bits per channel of a group-quantized row
     lrp_engine: str = "auto"                 # relevance pass: "auto" (HIP engine on a GPU, autograd on the CPU) |
                                              # "hip" | "autograd" (AttnLRP rules as torch autograd, any device)

@@ -42,9 +42,10 @@ class BoundaryConfig:
     method: str = "last_row"
     head_weights: torch.Tensor | None = None
     selection: str = "ratio"      # "ratio": int(ratio*S) least important; "top_rho": keep mass 1 - ratio
-    # head-group codecs (rgroup, mixed_rgroup_int8): the relevance pass's channel-group tables of the residual stream
-    # entering each layer - {"relevance", "sensitivity"} (codec.wire.load_group_tables) or a plain [layers][H / 64]
-    # relevance list - and the average bits per channel; without a table every group gets the same width
+    # head-group codecs (rgroup, rgroup_rot, mixed_rgroup_int8): the relevance pass's channel-group tables of the
+    # residual stream entering each layer - {"relevance", "sensitivity"} (codec.wire.load_group_tables) or a plain
+    # [layers][H / 64] relevance list - and the average bits per channel; without a table every group gets the same
+    # width
     group_relevance: object = None
     group_avg_bits: float = 4.0
 

@@ -56,6 +56,10 @@ GRID = [
     (8, "weighted_importance", "mixed_int4_int8", "-"), (8, "weighted_importance", "ref_int4_global", "-"),
     (8, "last_row", "mixed_rgroup_int8@3", "rel"), (8, "last_row", "mixed_rgroup_int8@3", "uniform"),
     (8, "weighted_importance", "rgroup@3", "rel"), (8, "weighted_importance", "rgroup@3", "uniform"),
+    # the head groups rotated by the 64-point Hadamard transform against the plain ones at the same bytes (rotation
+    # is expected to pay from 4 bits up and may lose at 3); the plans come from the unrotated tables
+    (8, "weighted_importance", "rgroup_rot@3", "uniform"), (8, "weighted_importance", "rgroup@4", "uniform"),
+    (8, "weighted_importance", "rgroup_rot@4", "uniform"), (8, "weighted_importance", "rgroup_rot@4", "sens"),
 ]
 
 
