@@ -63,6 +63,31 @@ __device__ __forceinline__ int row_bytes(const CodecArgs& a, int fmt) {
   return fmt == FMT_GRP ? a.grp_code_bytes + 4 * (a.H / 64) : fmt_row_bytes(fmt, a.H);
 }
 
+// Max-abs reductions of the codec propagate NaN (a unit holding a NaN / Inf must decode non-finite, and fmaxf drops a
+// NaN operand): they run on the bit pattern of |x| as an unsigned integer.  For non-negative floats the integer order
+// is the float order (denormals included), Inf is above every finite value and every NaN above Inf - the max of a
+// unit with a NaN is a NaN, with an Inf and no NaN Inf, and for finite values the very float fmaxf returns.
+// (wave_max / block_max of common.h keep fmaxf: their other users want it.)
+__device__ __forceinline__ uint32_t abs_bits(float x) { return __float_as_uint(x) & 0x7fffffffu; }
+__device__ __forceinline__ uint32_t umax(uint32_t a, uint32_t b) { return a > b ? a : b; }
+__device__ __forceinline__ uint32_t wave_umax(uint32_t v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = umax(v, __shfl_xor(v, o, 64));
+  return v;
+}
+template <int NT>
+__device__ __forceinline__ uint32_t block_umax(uint32_t v, uint32_t* red) {
+  v = wave_umax(v);
+  const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
+  if (l == 0) red[w] = v;
+  __syncthreads();
+  uint32_t t = 0;
+#pragma unroll
+  for (int i = 0; i < NT / 64; ++i) t = umax(t, red[i]);
+  __syncthreads();
+  return t;
+}
+
 __device__ __forceinline__ int wave_isum(int v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
@@ -188,30 +213,34 @@ __global__ __launch_bounds__(256) void channel_stats_kernel(const T* __restrict_
   const int b = blockIdx.x, c = blockIdx.y * 64 + (threadIdx.x & 63), rg = threadIdx.x >> 6;
   const uint32_t* mb = mask + (size_t)b * mask_stride;
   float acc = 0.f;
+  uint32_t am = 0;   // mode 0: bits of the running max|x| (NaN-propagating, see abs_bits)
   if (c < H) {
     for (int j = rg; j < S; j += 4) {
       if (only_lo && !((mb[j >> 5] >> (j & 31)) & 1u)) continue;
       const float xv = ldx(x, ((size_t)b * S + j) * H + c);
-      acc = mode == 0 ? fmaxf(acc, fabsf(xv)) : acc + xv;
+      if (mode == 0) am = umax(am, abs_bits(xv));
+      else acc += xv;
     }
   }
-  red[rg][threadIdx.x & 63] = acc;
+  red[rg][threadIdx.x & 63] = mode == 0 ? __uint_as_float(am) : acc;
   __syncthreads();
   if (rg == 0 && c < H) {
     const int l = threadIdx.x;
-    float r = mode == 0 ? fmaxf(fmaxf(red[0][l], red[1][l]), fmaxf(red[2][l], red[3][l]))
+    float r = mode == 0 ? __uint_as_float(umax(umax(__float_as_uint(red[0][l]), __float_as_uint(red[1][l])),
+                                               umax(__float_as_uint(red[2][l]), __float_as_uint(red[3][l]))))
                         : (red[0][l] + red[1][l]) + (red[2][l] + red[3][l]);
     out[(size_t)b * H + c] = mode == 0 ? r : r / (float)S + 1e-8f;
   }
 }
 
+// Row max of max-abs values (channel_stats mode 0: non-negative or NaN), NaN-propagating.
 __global__ __launch_bounds__(256) void rowmax_kernel(const float* __restrict__ in, float* __restrict__ out, int H) {
-  __shared__ float red[4];
+  __shared__ uint32_t red[4];
   const float* r = in + (size_t)blockIdx.x * H;
-  float m = 0.f;
-  for (int c = threadIdx.x; c < H; c += 256) m = fmaxf(m, r[c]);
-  m = block_max<256>(m, red);
-  if (threadIdx.x == 0) out[blockIdx.x] = m;
+  uint32_t m = 0;
+  for (int c = threadIdx.x; c < H; c += 256) m = umax(m, abs_bits(r[c]));
+  m = block_umax<256>(m, red);
+  if (threadIdx.x == 0) out[blockIdx.x] = __uint_as_float(m);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -252,9 +281,14 @@ __device__ __forceinline__ float qround(float t, float qmax, float qmin) { retur
 
 typedef __attribute__((ext_vector_type(2))) short s16x2_t;
 
-// E8M0 scale byte and value of a 32-channel block (4 lanes x 8 values): 2^(floor(log2 amax) - emax)
+// E8M0 scale byte and value of a 32-channel block (4 lanes x 8 values): 2^(floor(log2 amax) - emax); a block holding
+// a NaN / Inf (amax non-finite) gets byte 255, which OCP MX defines as NaN: mx_unpack8 decodes the whole block to NaN
+// (in software - nothing here depends on what the scaled converts do with an all-ones scale exponent).
+enum { MX_NAN = 255 };
 __device__ __forceinline__ int mx_scale_byte(float am, int emax) {
-  const int e = am > 0.f ? (int)((__float_as_uint(am) >> 23) & 0xff) - 127 : -127;   // denormal amax -> -127
+  const int ef = (int)((__float_as_uint(am) >> 23) & 0xff);
+  if (ef == 255) return MX_NAN;
+  const int e = am > 0.f ? ef - 127 : -127;   // denormal amax -> -127
   const int sb = e - emax + 127;
   return sb < 0 ? 0 : (sb > 254 ? 254 : sb);
 }
@@ -262,13 +296,13 @@ __device__ __forceinline__ float e8m0_value(int sb) { return sb ? __uint_as_floa
 
 __device__ __forceinline__ void mx_pack8(uint8_t* __restrict__ row, int H, int col, int fmt, const float (&v)[8]) {
   const int lane = threadIdx.x & 63;
-  float am = 0.f;
+  uint32_t amb = 0;
 #pragma unroll
-  for (int e = 0; e < 8; ++e) am = fmaxf(am, fabsf(v[e]));
-  am = fmaxf(am, __shfl_xor(am, 1, 64));
-  am = fmaxf(am, __shfl_xor(am, 2, 64));
-  const int sb = mx_scale_byte(am, fmt == FMT_MXFP4 ? 2 : 8);
-  const float X = e8m0_value(sb);
+  for (int e = 0; e < 8; ++e) amb = umax(amb, abs_bits(v[e]));
+  amb = umax(amb, __shfl_xor(amb, 1, 64));
+  amb = umax(amb, __shfl_xor(amb, 2, 64));
+  const int sb = mx_scale_byte(__uint_as_float(amb), fmt == FMT_MXFP4 ? 2 : 8);
+  const float X = e8m0_value(sb == MX_NAN ? 127 : sb);   // the codes of a NaN block are never read
   if (fmt == FMT_MXFP4) {
     uint32_t w = 0;
     w = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(w, v[0], v[1], X, 0);
@@ -297,18 +331,22 @@ __device__ __forceinline__ void mx_pack8(uint8_t* __restrict__ row, int H, int c
 }
 
 __device__ __forceinline__ void mx_unpack8(const uint8_t* __restrict__ row, int H, int col, int fmt, float (&o)[8]) {
+  const int sb = row[(fmt == FMT_MXFP4 ? H / 2 : H) + col / 32];
+  const float X = e8m0_value(sb == MX_NAN ? 127 : sb);
   if (fmt == FMT_MXFP4) {
-    const float X = e8m0_value(row[H / 2 + col / 32]);
     const uint32_t w = *(const uint32_t*)(row + col / 2);
     f32x2_t p0 = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(w, X, 0), p1 = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(w, X, 1);
     f32x2_t p2 = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(w, X, 2), p3 = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(w, X, 3);
     o[0] = p0[0]; o[1] = p0[1]; o[2] = p1[0]; o[3] = p1[1]; o[4] = p2[0]; o[5] = p2[1]; o[6] = p3[0]; o[7] = p3[1];
   } else {
-    const float X = e8m0_value(row[H + col / 32]);
     const u32x2_t w = *(const u32x2_t*)(row + col);
     f32x2_t p0 = __builtin_amdgcn_cvt_scalef32_pk_f32_fp8(w[0], X, false), p1 = __builtin_amdgcn_cvt_scalef32_pk_f32_fp8(w[0], X, true);
     f32x2_t p2 = __builtin_amdgcn_cvt_scalef32_pk_f32_fp8(w[1], X, false), p3 = __builtin_amdgcn_cvt_scalef32_pk_f32_fp8(w[1], X, true);
     o[0] = p0[0]; o[1] = p0[1]; o[2] = p1[0]; o[3] = p1[1]; o[4] = p2[0]; o[5] = p2[1]; o[6] = p3[0]; o[7] = p3[1];
+  }
+  if (sb == MX_NAN) {
+#pragma unroll
+    for (int e = 0; e < 8; ++e) o[e] = __builtin_nanf("");
   }
 }
 
@@ -357,12 +395,13 @@ __device__ __forceinline__ void grp_pack8(uint8_t* __restrict__ row, const Codec
   const uint8_t* plan = a.msg + a.off_plan;
   const int g = col >> 6, bits = plan[g];
   const int qmax = (1 << (bits - 1)) - 1;
-  float am = 0.f;
+  uint32_t amb = 0;
 #pragma unroll
-  for (int e = 0; e < 8; ++e) am = fmaxf(am, fabsf(v[e]));
-  am = fmaxf(am, __shfl_xor(am, 1, 64));
-  am = fmaxf(am, __shfl_xor(am, 2, 64));
-  am = fmaxf(am, __shfl_xor(am, 4, 64));
+  for (int e = 0; e < 8; ++e) amb = umax(amb, abs_bits(v[e]));
+  amb = umax(amb, __shfl_xor(amb, 1, 64));
+  amb = umax(amb, __shfl_xor(amb, 2, 64));
+  amb = umax(amb, __shfl_xor(amb, 4, 64));
+  const float am = __uint_as_float(amb);      // NaN / Inf if the group holds one: s, and the decode, non-finite
   const float s = am / (float)qmax;
   const float inv = am > 0.f ? 1.f / s : 0.f;
   const float qf = (float)qmax;
@@ -517,12 +556,12 @@ __global__ __launch_bounds__(256) void pack_kernel(CodecArgs a) {
   if (raw && a.scale_mode == SC_TOKEN && lane == 0) scales[row] = 0.f;
   if (!raw) {
     if (a.scale_mode == SC_TOKEN) {
-      float am = 0.f;
+      uint32_t amb = 0;
 #pragma unroll
       for (int c = 0; c < NCH; ++c)
 #pragma unroll
-        for (int e = 0; e < 8; ++e) am = fmaxf(am, fabsf(v[c][e]));
-      am = wave_max(am);
+        for (int e = 0; e < 8; ++e) amb = umax(amb, abs_bits(v[c][e]));
+      const float am = __uint_as_float(wave_umax(amb));   // NaN / Inf if the row holds one: s non-finite
       const float s = am / (float)qmax;
       if (lane == 0) scales[row] = s;
       inv = am > 0.f ? 1.f / s : 0.f;
@@ -754,9 +793,14 @@ EDGE_API int edge_select(const float* imp, int B, int S, int k, void* msg, long 
 
 // Constant lo-class mask (k = 0 or k = S): a kernel, not hipMemsetAsync - inside a captured HIP graph the memset node
 // was measured to lose its order against the message's zero fill (replays produced an all-zero mask for k = S).
-__global__ __launch_bounds__(256) void set_mask_kernel(uint32_t* __restrict__ mask, size_t nwords, uint32_t v) {
+// k = S sets the bits of the S tokens only - bit j <=> token j, as select_sort_kernel and the CPU codec write it: the
+// padding bits of a partial last word (S % 64 != 0) stay 0, so the message is the CPU's byte for byte.
+__global__ __launch_bounds__(256) void set_mask_kernel(uint32_t* __restrict__ mask, size_t nwords, int mw, int S,
+                                                       int all_lo) {
   const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (i < nwords) mask[i] = v;
+  if (i >= nwords) return;
+  const int n = S - 32 * (int)(i % (size_t)mw);   // tokens from this word's bit 0 on
+  mask[i] = !all_lo || n <= 0 ? 0u : n >= 32 ? 0xffffffffu : (1u << n) - 1u;
 }
 
 EDGE_API int edge_set_mask(void* msg, long long off_mask, int B, int S, int all_lo, hipStream_t st) {
@@ -764,8 +808,8 @@ EDGE_API int edge_set_mask(void* msg, long long off_mask, int B, int S, int all_
   const size_t n = (size_t)B * mw;
   if (!n) return 0;
   if (off_mask % 4) return (int)hipErrorInvalidValue;
-  set_mask_kernel<<<(unsigned)((n + 255) / 256), 256, 0, st>>>((uint32_t*)((uint8_t*)msg + off_mask), n,
-                                                                all_lo ? 0xffffffffu : 0u);
+  set_mask_kernel<<<(unsigned)((n + 255) / 256), 256, 0, st>>>((uint32_t*)((uint8_t*)msg + off_mask), n, mw, S,
+                                                                all_lo);
   return (int)hipGetLastError();
 }
 

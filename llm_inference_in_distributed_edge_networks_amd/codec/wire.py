@@ -23,6 +23,10 @@ the ``sum k`` lo rows (compact); its buffer (``Layout.total``) has capacity for 
 
 ``encode``/``decode`` run the gfx950 kernels of ``csrc/codec.hip`` for CUDA
 tensors and a bit-identical PyTorch implementation for CPU tensors.
+
+Non-finite activations stay loud: a unit (token row, head group, MX block, window, channel) that holds a NaN or an
+Inf decodes to non-finite values - its max-abs, and with it its scale, is non-finite on both sides; an MX block
+stores E8M0 byte 255.  Only the bytes of such a unit may differ between the GPU and the CPU (NaN payloads).
 """
 from __future__ import annotations
 
@@ -440,6 +444,9 @@ def _fp4_codes(v: torch.Tensor) -> torch.Tensor:
     return c | torch.signbit(v).to(torch.int64) << 3
 
 
+MX_NAN = 255                # E8M0 byte of a block that held a NaN / Inf (OCP: NaN): all 32 channels decode to NaN
+
+
 def _mx_exp(am: torch.Tensor, emax: int) -> torch.Tensor:
     """E8M0 scale byte: clamp(floor(log2 amax) - emax + 127, 0, 254); amax 0 / denormal -> exponent -127."""
     bits = am.float().contiguous().view(torch.int32).to(torch.int64)
@@ -456,8 +463,10 @@ def _e8m0(sb: torch.Tensor) -> torch.Tensor:
 def _mx_pack(rows: torch.Tensor, fmt: int) -> torch.Tensor:
     n, H = rows.shape
     blk = rows.float().reshape(n, H // 32, 32)
-    sb = _mx_exp(blk.abs().amax(-1), 2 if fmt == FMT_MXFP4 else 8)           # [n, H/32]
+    am = blk.abs().amax(-1)                                                  # NaN if the block holds one
+    sb = _mx_exp(am, 2 if fmt == FMT_MXFP4 else 8)                           # [n, H/32]
     y = blk / _e8m0(sb)[..., None]
+    sb = torch.where(torch.isfinite(am), sb, torch.full_like(sb, MX_NAN))    # codes of such a block: don't care
     if fmt == FMT_MXFP4:
         c = _fp4_codes(y).reshape(n, H // 2, 2)
         codes = (c[..., 0] | (c[..., 1] << 4)).to(torch.uint8)
@@ -475,7 +484,8 @@ def _mx_unpack(b: torch.Tensor, fmt: int, n: int, H: int) -> torch.Tensor:
         v = _FP4_GRID[c & 7] * torch.where(c >= 8, -1.0, 1.0)
     else:
         v = codes.contiguous().view(torch.float8_e4m3fn).float()
-    return (v.reshape(n, H // 32, 32) * _e8m0(sb)[..., None]).reshape(n, H)
+    out = v.reshape(n, H // 32, 32) * _e8m0(sb)[..., None]
+    return torch.where((sb == MX_NAN)[..., None], torch.full_like(out, float("nan")), out).reshape(n, H)
 
 
 def _grp_bits_pack(q: torch.Tensor, bits: int) -> torch.Tensor:
