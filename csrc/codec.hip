@@ -34,6 +34,9 @@ enum { FMT_BF16 = 0, FMT_INT8 = 1, FMT_INT4 = 2, FMT_INT2 = 3, FMT_F32 = 4, FMT_
 // for bit.  Messages with rows of this format run the ROT instantiations of pack_kernel / unpack_kernel
 // (pack_kernel<NCH, T, true>, every rotated branch under `if constexpr (ROT)`), so the instantiations every other
 // codec runs keep their instruction stream.
+// One definition each, shared by pack_kernel and unpack_kernel: row_slot<ROT> (a row's class, format, qmax, window and
+// message address: the fixed-k / variable-k addressing), SELF_SCALED (the formats with no entry in the scale
+// section), grp_walk (a group's stream offset and width from the message's plan bytes, and whether they are usable).
 // OCP microscaling rows (FMT_MXFP4: E2M1 codes, FMT_MXFP8: E4M3 codes): blocks of 32 consecutive channels share one
 // E8M0 scale 2^(floor(log2 max|x|) - emax) (emax 2 / 8), stored after the row's codes: [codes][H/32 scale bytes].
 // Quantize / dequantize with gfx950's scaled converts (v_cvt_scalef32_pk_fp4_f32 / _fp8_f32 and the inverses:
@@ -62,6 +65,12 @@ __device__ __forceinline__ int row_bytes(const CodecArgs& a, int fmt) {
   }
   return fmt == FMT_GRP ? a.grp_code_bytes + 4 * (a.H / 64) : fmt_row_bytes(fmt, a.H);
 }
+// Formats whose rows carry their own scales (or none): no entry in the message's scale section.  A macro, and the
+// rotated format joined with `|`: the compiler simplifies the body of an inlined function on its own first, and the
+// rotated pack instantiations then allocate 66 / 82 instead of 56 / 74 VGPRs (NCH 2 / 4: a wave per SIMD less).
+#define SELF_SCALED(ROT, fmt) \
+  (((fmt) == FMT_BF16 || (fmt) == FMT_F32 || (fmt) == FMT_MXFP4 || (fmt) == FMT_MXFP8 || (fmt) == FMT_GRP) | \
+   ((ROT) && (fmt) == FMT_GRPR))
 
 // Max-abs reductions of the codec propagate NaN (a unit holding a NaN / Inf must decode non-finite, and fmaxf drops a
 // NaN operand): they run on the bit pattern of |x| as an unsigned integer.  For non-negative floats the integer order
@@ -70,6 +79,16 @@ __device__ __forceinline__ int row_bytes(const CodecArgs& a, int fmt) {
 // (wave_max / block_max of common.h keep fmaxf: their other users want it.)
 __device__ __forceinline__ uint32_t abs_bits(float x) { return __float_as_uint(x) & 0x7fffffffu; }
 __device__ __forceinline__ uint32_t umax(uint32_t a, uint32_t b) { return a > b ? a : b; }
+__device__ __forceinline__ uint32_t umax8(const float (&v)[8]) {   // bits of max|v|
+  uint32_t m = 0;
+#pragma unroll
+  for (int e = 0; e < 8; ++e) m = umax(m, abs_bits(v[e]));
+  return m;
+}
+__device__ __forceinline__ void fill8(float (&o)[8], float x) {
+#pragma unroll
+  for (int e = 0; e < 8; ++e) o[e] = x;
+}
 __device__ __forceinline__ uint32_t wave_umax(uint32_t v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v = umax(v, __shfl_xor(v, o, 64));
@@ -199,6 +218,32 @@ __device__ __forceinline__ void kvar_prefix(const CodecArgs& a, int b, int& Kb, 
   Kt = wave_isum(all);
 }
 
+// Where row `row` (token j of window b) lives in the message and how it is coded: its class from the mask, its slot
+// among the class's rows of its window (lo_prefix), the class's rows of the windows before (b k / b (S - k) for fixed
+// k, the k vector's prefix sum for variable k, whose hi section starts right after the Sum k lo rows).
+struct RowSlot { uint8_t* p; int fmt, qmax, b; };
+template <bool ROT>
+__device__ __forceinline__ RowSlot row_slot(const CodecArgs& a, int row) {
+  const int b = row / a.S, j = row - b * a.S;
+  const uint32_t* mask = (const uint32_t*)(a.msg + a.off_mask) + (size_t)b * a.mw;
+  bool is_lo;
+  const int slot_lo = lo_prefix(mask, a.mw, j, is_lo);
+  const int fmt = is_lo ? a.lo_fmt : a.hi_fmt;
+  const int rb = row_bytes<ROT>(a, fmt);
+  uint8_t* p;
+  if (a.off_kvec >= 0) {
+    int Kb, Kt;
+    kvar_prefix(a, b, Kb, Kt);
+    const long long off_hi = a.off_lo + (((long long)Kt * row_bytes<ROT>(a, a.lo_fmt) + 15) & ~15ll);
+    p = is_lo ? a.msg + a.off_lo + ((size_t)Kb + slot_lo) * rb
+              : a.msg + off_hi + ((size_t)b * a.S - Kb + (j - slot_lo)) * rb;
+  } else {
+    p = is_lo ? a.msg + a.off_lo + ((size_t)b * a.k + slot_lo) * rb
+              : a.msg + a.off_hi + ((size_t)b * (a.S - a.k) + (j - slot_lo)) * rb;
+  }
+  return {p, fmt, is_lo ? a.qmax_lo : a.qmax_hi, b};
+}
+
 // Per-(window, channel) statistics over the window's rows (optionally only lo-class rows).
 // mode 0: max|x|, mode 1: mean(x) + 1e-8.   grid (B, ceil(H/64)), 256 threads = 4 row groups x 64 ch.
 __device__ __forceinline__ float ldx(const bf16_t* p, size_t i) { return bf2f(p[i]); }
@@ -296,9 +341,7 @@ __device__ __forceinline__ float e8m0_value(int sb) { return sb ? __uint_as_floa
 
 __device__ __forceinline__ void mx_pack8(uint8_t* __restrict__ row, int H, int col, int fmt, const float (&v)[8]) {
   const int lane = threadIdx.x & 63;
-  uint32_t amb = 0;
-#pragma unroll
-  for (int e = 0; e < 8; ++e) amb = umax(amb, abs_bits(v[e]));
+  uint32_t amb = umax8(v);
   amb = umax(amb, __shfl_xor(amb, 1, 64));
   amb = umax(amb, __shfl_xor(amb, 2, 64));
   const int sb = mx_scale_byte(__uint_as_float(amb), fmt == FMT_MXFP4 ? 2 : 8);
@@ -330,6 +373,9 @@ __device__ __forceinline__ void mx_pack8(uint8_t* __restrict__ row, int H, int c
   }
 }
 
+__device__ __forceinline__ void put4(float (&o)[8], f32x2_t p0, f32x2_t p1, f32x2_t p2, f32x2_t p3) {
+  o[0] = p0[0]; o[1] = p0[1]; o[2] = p1[0]; o[3] = p1[1]; o[4] = p2[0]; o[5] = p2[1]; o[6] = p3[0]; o[7] = p3[1];
+}
 __device__ __forceinline__ void mx_unpack8(const uint8_t* __restrict__ row, int H, int col, int fmt, float (&o)[8]) {
   const int sb = row[(fmt == FMT_MXFP4 ? H / 2 : H) + col / 32];
   const float X = e8m0_value(sb == MX_NAN ? 127 : sb);
@@ -337,17 +383,14 @@ __device__ __forceinline__ void mx_unpack8(const uint8_t* __restrict__ row, int 
     const uint32_t w = *(const uint32_t*)(row + col / 2);
     f32x2_t p0 = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(w, X, 0), p1 = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(w, X, 1);
     f32x2_t p2 = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(w, X, 2), p3 = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(w, X, 3);
-    o[0] = p0[0]; o[1] = p0[1]; o[2] = p1[0]; o[3] = p1[1]; o[4] = p2[0]; o[5] = p2[1]; o[6] = p3[0]; o[7] = p3[1];
+    put4(o, p0, p1, p2, p3);
   } else {
     const u32x2_t w = *(const u32x2_t*)(row + col);
     f32x2_t p0 = __builtin_amdgcn_cvt_scalef32_pk_f32_fp8(w[0], X, false), p1 = __builtin_amdgcn_cvt_scalef32_pk_f32_fp8(w[0], X, true);
     f32x2_t p2 = __builtin_amdgcn_cvt_scalef32_pk_f32_fp8(w[1], X, false), p3 = __builtin_amdgcn_cvt_scalef32_pk_f32_fp8(w[1], X, true);
-    o[0] = p0[0]; o[1] = p0[1]; o[2] = p1[0]; o[3] = p1[1]; o[4] = p2[0]; o[5] = p2[1]; o[6] = p3[0]; o[7] = p3[1];
+    put4(o, p0, p1, p2, p3);
   }
-  if (sb == MX_NAN) {
-#pragma unroll
-    for (int e = 0; e < 8; ++e) o[e] = __builtin_nanf("");
-  }
+  if (sb == MX_NAN) fill8(o, __builtin_nanf(""));
 }
 
 // FMT_GRP: the 8 lanes holding channels [64 g, 64 g + 64) of a row (8 values each) quantize their group.
@@ -395,9 +438,7 @@ __device__ __forceinline__ void grp_pack8(uint8_t* __restrict__ row, const Codec
   const uint8_t* plan = a.msg + a.off_plan;
   const int g = col >> 6, bits = plan[g];
   const int qmax = (1 << (bits - 1)) - 1;
-  uint32_t amb = 0;
-#pragma unroll
-  for (int e = 0; e < 8; ++e) amb = umax(amb, abs_bits(v[e]));
+  uint32_t amb = umax8(v);
   amb = umax(amb, __shfl_xor(amb, 1, 64));
   amb = umax(amb, __shfl_xor(amb, 2, 64));
   amb = umax(amb, __shfl_xor(amb, 4, 64));
@@ -413,16 +454,14 @@ __device__ __forceinline__ void grp_pack8(uint8_t* __restrict__ row, const Codec
   grp_store(row + grp_offset(plan, g) + sub * bits, w, bits);
   if (sub == 0) *(float*)(row + a.grp_code_bytes + 4 * g) = s;
 }
+// A group's place in a row as the MESSAGE's plan bytes give it, for the decoders: byte offset of its stream (never
+// negative: unsigned), its width, and `bad`: a width outside GROUP_BITS (a corrupt or version-mismatched message) in
+// this group or one before it, or a group stream reaching past the row's code bytes.  A bad group decodes to NaN -
+// loud - instead of a shift by 32 or a read past the row (invalid widths count 0 bytes in the offset).
 __device__ __forceinline__ bool grp_bits_ok(int b) { return b == 2 || b == 3 || b == 4 || b == 5 || b == 6 || b == 8; }
-__device__ __forceinline__ void grp_unpack8(const uint8_t* __restrict__ row, const CodecArgs& a, int col,
-                                            float (&o)[8]) {
-  const int lane = threadIdx.x & 63;
+struct GrpWalk { uint32_t off; int bits; bool bad; };
+__device__ __forceinline__ GrpWalk grp_walk(const CodecArgs& a, int g) {
   const uint8_t* plan = a.msg + a.off_plan;
-  const int g = col >> 6;
-  const int sub = lane & 7;
-  // the plan bytes come from the message: a width outside GROUP_BITS (a corrupt or version-mismatched message) or a
-  // group stream reaching past the row's code bytes decodes to NaN - loud - instead of a shift by 32 or a read past
-  // the row (invalid widths count 0 bytes in the offset)
   int off = 0;
   bool bad = false;
   for (int i = 0; i < g; ++i) {
@@ -432,18 +471,26 @@ __device__ __forceinline__ void grp_unpack8(const uint8_t* __restrict__ row, con
   }
   const int bits = plan[g];
   bad |= !grp_bits_ok(bits) || off + 8 * bits > a.grp_code_bytes;
-  if (bad) {
-#pragma unroll
-    for (int e = 0; e < 8; ++e) o[e] = __builtin_nanf("");
+  return {(uint32_t)off, bits, bad};
+}
+// Code e of a lane's 8: the sign-extended b-bit field at bit b e of its b bytes.
+__device__ __forceinline__ int grp_code(uint64_t w, int bits, int e) {
+  return ((int)((uint32_t)(w >> (bits * e)) << (32 - bits))) >> (32 - bits);
+}
+__device__ __forceinline__ void grp_unpack8(const uint8_t* __restrict__ row, const CodecArgs& a, int col,
+                                            float (&o)[8]) {
+  const int lane = threadIdx.x & 63;
+  const int g = col >> 6, sub = lane & 7;
+  const GrpWalk k = grp_walk(a, g);
+  const int bits = k.bits;
+  if (k.bad) {
+    fill8(o, __builtin_nanf(""));
     return;
   }
-  const uint64_t w = grp_load(row + off + sub * bits, bits);
+  const uint64_t w = grp_load(row + k.off + sub * bits, bits);
   const float s = *(const float*)(row + a.grp_code_bytes + 4 * g);
 #pragma unroll
-  for (int e = 0; e < 8; ++e) {
-    const int q = ((int)((uint32_t)(w >> (bits * e)) << (32 - bits))) >> (32 - bits);   // sign-extend b bits
-    o[e] = (float)q * s;
-  }
+  for (int e = 0; e < 8; ++e) o[e] = (float)grp_code(w, bits, e) * s;
 }
 
 // FMT_GRPR: the unnormalised 64-point Walsh-Hadamard transform of a group held 8 consecutive channels per lane by the
@@ -487,39 +534,30 @@ __device__ __forceinline__ void grp_pack8_rot(uint8_t* __restrict__ row, const C
   for (int e = 0; e < 8; ++e) y[e] *= 0.125f;
   grp_pack8(row, a, col, y);
 }
-// As grp_unpack8 (NaN from the first bad group on), but `bad` - uniform over the group's 8 lanes - only zeroes the
-// codes before the shuffles and is applied after them, so no lane of a group leaves early.
+// As grp_unpack8 (NaN from the first bad group on), but a bad group - uniform over the group's 8 lanes - only zeroes
+// the codes before the shuffles and is applied after them, so no lane of a group leaves early.
 __device__ __forceinline__ void grp_unpack8_rot(const uint8_t* __restrict__ row, const CodecArgs& a, int col,
                                                 float (&o)[8]) {
   const int lane = threadIdx.x & 63;
-  const uint8_t* plan = a.msg + a.off_plan;
-  const int g = col >> 6;
-  const int sub = lane & 7;
-  int off = 0;
-  bool bad = false;
-  for (int i = 0; i < g; ++i) {
-    const int b = plan[i];
-    bad |= !grp_bits_ok(b);
-    off += grp_bits_ok(b) ? 8 * b : 0;
-  }
-  const int bits = plan[g];
-  bad |= !grp_bits_ok(bits) || off + 8 * bits > a.grp_code_bytes;
+  const int g = col >> 6, sub = lane & 7;
+  const GrpWalk k = grp_walk(a, g);
+  const int bits = k.bits;
   int q[8];
   float s = 0.f;
-  if (bad) {
-#pragma unroll
-    for (int e = 0; e < 8; ++e) q[e] = 0;
-  } else {
-    const uint64_t w = grp_load(row + off + sub * bits, bits);
+  if (!k.bad) {
+    const uint64_t w = grp_load(row + k.off + sub * bits, bits);
     s = *(const float*)(row + a.grp_code_bytes + 4 * g);
 #pragma unroll
-    for (int e = 0; e < 8; ++e) q[e] = ((int)((uint32_t)(w >> (bits * e)) << (32 - bits))) >> (32 - bits);
+    for (int e = 0; e < 8; ++e) q[e] = grp_code(w, bits, e);
+  } else {
+#pragma unroll
+    for (int e = 0; e < 8; ++e) q[e] = 0;
   }
   wht8(q);
   wht_lanes(q);
   const float sc = s * 0.125f;
 #pragma unroll
-  for (int e = 0; e < 8; ++e) o[e] = bad ? __builtin_nanf("") : (float)q[e] * sc;
+  for (int e = 0; e < 8; ++e) o[e] = k.bad ? __builtin_nanf("") : (float)q[e] * sc;
 }
 
 template <int NCH, class T, bool ROT = false>
@@ -527,32 +565,16 @@ __global__ __launch_bounds__(256) void pack_kernel(CodecArgs a) {
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= a.B * a.S) return;
   const int lane = threadIdx.x & 63;
-  const int b = row / a.S, j = row - b * a.S;
-  const uint32_t* mask = (const uint32_t*)(a.msg + a.off_mask) + (size_t)b * a.mw;
-  bool is_lo;
-  const int slot_lo = lo_prefix(mask, a.mw, j, is_lo);
-  const int fmt = is_lo ? a.lo_fmt : a.hi_fmt;
-  const int qmax = is_lo ? a.qmax_lo : a.qmax_hi;
-  const int rb = row_bytes<ROT>(a, fmt);
-  uint8_t* dst;
-  if (a.off_kvec >= 0) {
-    int Kb, Kt;
-    kvar_prefix(a, b, Kb, Kt);
-    const long long off_hi = a.off_lo + (((long long)Kt * row_bytes<ROT>(a, a.lo_fmt) + 15) & ~15ll);
-    dst = is_lo ? a.msg + a.off_lo + ((size_t)Kb + slot_lo) * rb
-                : a.msg + off_hi + ((size_t)b * a.S - Kb + (j - slot_lo)) * rb;
-  } else {
-    dst = is_lo ? a.msg + a.off_lo + ((size_t)b * a.k + slot_lo) * rb
-                : a.msg + a.off_hi + ((size_t)b * (a.S - a.k) + (j - slot_lo)) * rb;
-  }
+  const RowSlot rs = row_slot<ROT>(a, row);
+  uint8_t* dst = rs.p;
+  const int fmt = rs.fmt, qmax = rs.qmax, b = rs.b;
   float v[NCH][8];
   load_row8<NCH>((const T*)a.x + (size_t)row * a.H, a.H, v);
   float* scales = (float*)(a.msg + a.off_scale);
 
   // scale / quantiser for this row
   float inv = 0.f, mul = 0.f;  // code = round(x * inv) for token & channel; window mode uses ref formula
-  bool raw = fmt == FMT_BF16 || fmt == FMT_F32 || fmt == FMT_MXFP4 || fmt == FMT_MXFP8 || fmt == FMT_GRP;
-  if constexpr (ROT) raw |= fmt == FMT_GRPR;
+  const bool raw = SELF_SCALED(ROT, fmt);
   if (raw && a.scale_mode == SC_TOKEN && lane == 0) scales[row] = 0.f;
   if (!raw) {
     if (a.scale_mode == SC_TOKEN) {
@@ -656,28 +678,12 @@ __global__ __launch_bounds__(256) void unpack_kernel(CodecArgs a) {
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= a.B * a.S) return;
   const int lane = threadIdx.x & 63;
-  const int b = row / a.S, j = row - b * a.S;
-  const uint32_t* mask = (const uint32_t*)(a.msg + a.off_mask) + (size_t)b * a.mw;
-  bool is_lo;
-  const int slot_lo = lo_prefix(mask, a.mw, j, is_lo);
-  const int fmt = is_lo ? a.lo_fmt : a.hi_fmt;
-  const int qmax = is_lo ? a.qmax_lo : a.qmax_hi;
-  const int rb = row_bytes<ROT>(a, fmt);
-  const uint8_t* src;
-  if (a.off_kvec >= 0) {
-    int Kb, Kt;
-    kvar_prefix(a, b, Kb, Kt);
-    const long long off_hi = a.off_lo + (((long long)Kt * row_bytes<ROT>(a, a.lo_fmt) + 15) & ~15ll);
-    src = is_lo ? a.msg + a.off_lo + ((size_t)Kb + slot_lo) * rb
-                : a.msg + off_hi + ((size_t)b * a.S - Kb + (j - slot_lo)) * rb;
-  } else {
-    src = is_lo ? a.msg + a.off_lo + ((size_t)b * a.k + slot_lo) * rb
-                : a.msg + a.off_hi + ((size_t)b * (a.S - a.k) + (j - slot_lo)) * rb;
-  }
+  const RowSlot rs = row_slot<ROT>(a, row);
+  const uint8_t* src = rs.p;
+  const int fmt = rs.fmt, qmax = rs.qmax, b = rs.b;
   const float* scales = (const float*)(a.msg + a.off_scale);
   float s = 0.f;
-  if (fmt != FMT_BF16 && fmt != FMT_F32 && fmt != FMT_MXFP4 && fmt != FMT_MXFP8 && fmt != FMT_GRP &&
-      !(ROT && fmt == FMT_GRPR)) {
+  if (!SELF_SCALED(ROT, fmt)) {
     if (a.scale_mode == SC_TOKEN) s = scales[row];
     else if (a.scale_mode == SC_WINDOW) s = scales[b];
   }
@@ -762,18 +768,7 @@ __global__ __launch_bounds__(256) void unpack_kernel(CodecArgs a) {
     else return (int)hipErrorInvalidValue;                            \
   } while (0)
 
-static CodecArgs make_args(void* x, void* msg, long long om, long long os, long long oh, long long ol, long long okv,
-                           long long opl, int B, int S, int H, int k, int hi_fmt, int lo_fmt, int scale_mode,
-                           int qmax_hi, int qmax_lo, int ch_kind, int grp_code_bytes) {
-  CodecArgs a;
-  a.x = x; a.msg = (uint8_t*)msg;
-  a.off_mask = om; a.off_scale = os; a.off_hi = oh; a.off_lo = ol; a.off_kvec = okv; a.off_plan = opl;
-  a.grp_code_bytes = grp_code_bytes;
-  a.B = B; a.S = S; a.H = H; a.k = k; a.mw = ((S + 63) / 64) * 2;
-  a.hi_fmt = hi_fmt; a.lo_fmt = lo_fmt; a.scale_mode = scale_mode; a.qmax_hi = qmax_hi; a.qmax_lo = qmax_lo;
-  a.ch_kind = ch_kind;
-  return a;
-}
+static int mask_words(int S) { return ((S + 63) / 64) * 2; }   // per window: whole 64-token pairs of u32
 
 // mode 0: k least important per window; mode 1: top-rho cut at mass thr, k per window -> msg + off_kvec (int32).
 EDGE_API int edge_select(const float* imp, int B, int S, int k, void* msg, long long off_mask, int mode, float thr,
@@ -782,7 +777,7 @@ EDGE_API int edge_select(const float* imp, int B, int S, int k, void* msg, long 
   if (S <= 0 || S > 8192 || (mode == 1 && off_kvec < 0)) return (int)hipErrorInvalidValue;
   int P = 1;
   while (P < S) P <<= 1;
-  const int mw = ((S + 63) / 64) * 2;
+  const int mw = mask_words(S);
   const size_t lds = (size_t)P * 8 + (size_t)mw * 4;
   if (lds > 65536) (void)hipFuncSetAttribute((const void*)select_sort_kernel,
                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -804,7 +799,7 @@ __global__ __launch_bounds__(256) void set_mask_kernel(uint32_t* __restrict__ ma
 }
 
 EDGE_API int edge_set_mask(void* msg, long long off_mask, int B, int S, int all_lo, hipStream_t st) {
-  const int mw = ((S + 63) / 64) * 2;
+  const int mw = mask_words(S);
   const size_t n = (size_t)B * mw;
   if (!n) return 0;
   if (off_mask % 4) return (int)hipErrorInvalidValue;
@@ -817,7 +812,7 @@ EDGE_API int edge_set_mask(void* msg, long long off_mask, int B, int S, int all_
 EDGE_API int edge_channel_stats(const void* x, const void* msg, long long off_mask, float* out, int B, int S, int H,
                                 int mode, int only_lo, int x_f32, hipStream_t st) {
   if (B <= 0) return 0;
-  const int mw = ((S + 63) / 64) * 2;
+  const int mw = mask_words(S);
   const uint32_t* mask = (const uint32_t*)((const uint8_t*)msg + off_mask);
   if (x_f32)
     hipLaunchKernelGGL(channel_stats_kernel<float>, dim3(B, (H + 63) / 64), dim3(256), 0, st, (const float*)x, mask,
@@ -838,41 +833,49 @@ EDGE_API int edge_rowmax(const float* in, float* out, int R, int H, hipStream_t 
 // A message with FMT_GRPR rows goes to the ROT instantiations (which handle every other format too).
 static bool has_fmt(int hi_fmt, int lo_fmt, int fmt) { return hi_fmt == fmt || lo_fmt == fmt; }
 
-EDGE_API int edge_pack(const void* x, void* msg, long long om, long long os, long long oh, long long ol, long long okv,
-                       long long opl, int B, int S, int H, int k, int hi_fmt, int lo_fmt, int scale_mode, int qmax_hi,
-                       int qmax_lo, int ch_kind, int grp_code_bytes, int x_f32, hipStream_t st) {
+template <bool PACK, int NCH, class T, bool ROT>
+static void launch_codec(dim3 grid, hipStream_t st, const CodecArgs& a) {
+  if constexpr (PACK) hipLaunchKernelGGL((pack_kernel<NCH, T, ROT>), grid, dim3(256), 0, st, a);
+  else hipLaunchKernelGGL((unpack_kernel<NCH, T, ROT>), grid, dim3(256), 0, st, a);
+}
+
+// edge_pack / edge_unpack: argument checks, CodecArgs and the (ROT x activation dtype) x NCH dispatch.
+template <bool PACK>
+static int run_codec(void* x, void* msg, long long om, long long os, long long oh, long long ol, long long okv,
+                     long long opl, int B, int S, int H, int k, int hi_fmt, int lo_fmt, int scale_mode, int qmax_hi,
+                     int qmax_lo, int ch_kind, int grp_code_bytes, int x_f32, hipStream_t st) {
   if (H % 32) return (int)hipErrorInvalidValue;
   const bool rot = has_fmt(hi_fmt, lo_fmt, FMT_GRPR);
   if ((rot || has_fmt(hi_fmt, lo_fmt, FMT_GRP)) && (H % 64 || opl < 0 || grp_code_bytes <= 0))
     return (int)hipErrorInvalidValue;
-  CodecArgs a = make_args((void*)x, msg, om, os, oh, ol, okv, opl, B, S, H, k, hi_fmt, lo_fmt, scale_mode, qmax_hi,
-                          qmax_lo, ch_kind, grp_code_bytes);
+  CodecArgs a;
+  a.x = x; a.msg = (uint8_t*)msg;
+  a.off_mask = om; a.off_scale = os; a.off_hi = oh; a.off_lo = ol; a.off_kvec = okv; a.off_plan = opl;
+  a.grp_code_bytes = grp_code_bytes;
+  a.B = B; a.S = S; a.H = H; a.k = k; a.mw = mask_words(S);
+  a.hi_fmt = hi_fmt; a.lo_fmt = lo_fmt; a.scale_mode = scale_mode; a.qmax_hi = qmax_hi; a.qmax_lo = qmax_lo;
+  a.ch_kind = ch_kind;
   const int rows = B * S;
   if (rows <= 0) return 0;
-  const dim3 grid((rows + 3) / 4), block(256);
-  if (rot && x_f32) DISPATCH_NCH(H, hipLaunchKernelGGL((pack_kernel<NCH, float, true>), grid, block, 0, st, a));
-  else if (rot) DISPATCH_NCH(H, hipLaunchKernelGGL((pack_kernel<NCH, bf16_t, true>), grid, block, 0, st, a));
-  else if (x_f32) DISPATCH_NCH(H, hipLaunchKernelGGL((pack_kernel<NCH, float>), grid, block, 0, st, a));
-  else DISPATCH_NCH(H, hipLaunchKernelGGL((pack_kernel<NCH, bf16_t>), grid, block, 0, st, a));
+  const dim3 grid((rows + 3) / 4);
+  if (rot && x_f32) DISPATCH_NCH(H, (launch_codec<PACK, NCH, float, true>(grid, st, a)));
+  else if (rot) DISPATCH_NCH(H, (launch_codec<PACK, NCH, bf16_t, true>(grid, st, a)));
+  else if (x_f32) DISPATCH_NCH(H, (launch_codec<PACK, NCH, float, false>(grid, st, a)));
+  else DISPATCH_NCH(H, (launch_codec<PACK, NCH, bf16_t, false>(grid, st, a)));
   return (int)hipGetLastError();
+}
+
+EDGE_API int edge_pack(const void* x, void* msg, long long om, long long os, long long oh, long long ol, long long okv,
+                       long long opl, int B, int S, int H, int k, int hi_fmt, int lo_fmt, int scale_mode, int qmax_hi,
+                       int qmax_lo, int ch_kind, int grp_code_bytes, int x_f32, hipStream_t st) {
+  return run_codec<true>((void*)x, msg, om, os, oh, ol, okv, opl, B, S, H, k, hi_fmt, lo_fmt, scale_mode, qmax_hi,
+                         qmax_lo, ch_kind, grp_code_bytes, x_f32, st);
 }
 
 EDGE_API int edge_unpack(void* x, const void* msg, long long om, long long os, long long oh, long long ol,
                          long long okv, long long opl, int B, int S, int H, int k, int hi_fmt, int lo_fmt,
                          int scale_mode, int qmax_hi, int qmax_lo, int ch_kind, int grp_code_bytes, int x_f32,
                          hipStream_t st) {
-  if (H % 32) return (int)hipErrorInvalidValue;
-  const bool rot = has_fmt(hi_fmt, lo_fmt, FMT_GRPR);
-  if ((rot || has_fmt(hi_fmt, lo_fmt, FMT_GRP)) && (H % 64 || opl < 0 || grp_code_bytes <= 0))
-    return (int)hipErrorInvalidValue;
-  CodecArgs a = make_args(x, (void*)msg, om, os, oh, ol, okv, opl, B, S, H, k, hi_fmt, lo_fmt, scale_mode, qmax_hi,
-                          qmax_lo, ch_kind, grp_code_bytes);
-  const int rows = B * S;
-  if (rows <= 0) return 0;
-  const dim3 grid((rows + 3) / 4), block(256);
-  if (rot && x_f32) DISPATCH_NCH(H, hipLaunchKernelGGL((unpack_kernel<NCH, float, true>), grid, block, 0, st, a));
-  else if (rot) DISPATCH_NCH(H, hipLaunchKernelGGL((unpack_kernel<NCH, bf16_t, true>), grid, block, 0, st, a));
-  else if (x_f32) DISPATCH_NCH(H, hipLaunchKernelGGL((unpack_kernel<NCH, float>), grid, block, 0, st, a));
-  else DISPATCH_NCH(H, hipLaunchKernelGGL((unpack_kernel<NCH, bf16_t>), grid, block, 0, st, a));
-  return (int)hipGetLastError();
+  return run_codec<false>(x, (void*)msg, om, os, oh, ol, okv, opl, B, S, H, k, hi_fmt, lo_fmt, scale_mode, qmax_hi,
+                          qmax_lo, ch_kind, grp_code_bytes, x_f32, st);
 }

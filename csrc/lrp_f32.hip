@@ -819,7 +819,7 @@ __global__ __launch_bounds__(256) void lrp_ln_bwd_f32_kernel(const float* __rest
 // 64 channels of |x dx|.  One workgroup per (window, group); deterministic (no atomics).
 // sens (optional): the group's quantization sensitivity sum over tokens t of max_c |x_tc|^2 * sum_c dx_tc^2 - the
 // expected squared first-order output change of a max-abs quantizer of step max_c |x_tc| / qmax is that over 12 qmax^2
-// (codec.wire.allocate_group_bits).  Wave w takes tokens w, w + 4, ...; its 64 lanes are the group's channels.
+// (codec.plan.allocate_group_bits).  Wave w takes tokens w, w + 4, ...; its 64 lanes are the group's channels.
 __global__ __launch_bounds__(256) void group_absprod_kernel(const float* __restrict__ x, const float* __restrict__ dx,
                                                             float* __restrict__ out, float* __restrict__ sens, int S,
                                                             int H, int G, int ob) {

@@ -35,7 +35,7 @@ rgroup_rot             rotated groups  --              per group    rgroup's byt
 =====================  ==============  ==============  ===========  ==================================
 
 Head-group codecs carry their group bit plan in the message; a boundary's plan comes from
-``wire.allocate_group_bits`` over the LRP relevance of its 64-channel groups (uniform without a table).
+``plan.allocate_group_bits`` over the LRP relevance of its 64-channel groups (uniform without a table).
 
 ``rgroup_rot`` rotates every group with the orthonormal Hadamard matrix before quantizing and back after
 dequantizing (integer butterflies on the codes, bit-identical on CPU and GPU), so a massive channel no longer sets
@@ -47,6 +47,7 @@ sensitivity / relevance tables; a table for rotated groups needs ``max_c |(H x)_
 "hi"/"lo" classes: the ``k = int(ratio * S)`` least important tokens of a
 window (ascending importance, ties broken by position) are the lo class.
 """
+from . import plan  # noqa: F401  (codec.plan: the head-group bit plans)
 from .wire import (CODECS, CodecSpec, Layout, decode, encode, fake_quant, get_codec, layout, message_bytes,
                    select_mask)
 

@@ -30,8 +30,10 @@ stores E8M0 byte 255.  Only the bytes of such a unit may differ between the GPU 
 """
 from __future__ import annotations
 
+import math
 from dataclasses import dataclass
 from functools import lru_cache
+from typing import Callable
 
 import torch
 
@@ -108,105 +110,6 @@ def with_plan(spec: CodecSpec, plan) -> CodecSpec:
     return replace(spec, plan=plan)
 
 
-def boundary_group_relevance(table, boundary: int, groups: int) -> list:
-    """The channel-group relevance of the tensor crossing the boundary after layer ``boundary`` from a
-    [layers][groups] table of the relevance ENTERING each layer (``channel_group_relevance.json``): row
-    ``boundary + 1``.  After the last layer the tensor is the final norm's input, which the table does not hold;
-    its last row (the stream entering the last layer) stands in.  No table: every group equal.  A dict table
-    ``{"relevance": ..., "sensitivity": ...}`` (``load_group_tables``) gives its relevance."""
-    if isinstance(table, dict):
-        table = table.get("relevance")
-    if table is None:
-        return [1.0] * groups
-    t = torch.as_tensor(table, dtype=torch.float32)
-    return [float(v) for v in t[min(boundary + 1, t.shape[0] - 1)]]
-
-
-def boundary_group_plan(table, boundary: int, groups: int, avg_bits: float = 4.0) -> tuple:
-    """The bit plan of the head-group codec at the boundary after layer ``boundary``.
-
-    ``table`` = ``{"relevance": [layers][G], "sensitivity": [layers][G]}`` (``load_group_tables``): the MSE
-    allocation over the groups' quantization sensitivity when it is there (``allocate_group_bits(model="mse")``),
-    else the first-order allocation over the LRP relevance (``model="linear"``, the round-3 allocator); a plain
-    [layers][G] list is a relevance table; None: the uniform plan (every group at ``avg_bits`` when that is a
-    width, else the MSE allocation of equal weights: the nearest widths, as evenly as the budget allows)."""
-    if table is None:
-        return allocate_group_bits([1.0] * groups, avg_bits, model="mse")
-    if isinstance(table, dict) and table.get("sensitivity") is not None:
-        w = boundary_group_relevance({"relevance": table["sensitivity"]}, boundary, groups)
-        return allocate_group_bits(w, avg_bits, model="mse")
-    return allocate_group_bits(boundary_group_relevance(table, boundary, groups), avg_bits, model="linear")
-
-
-def _qmax(bits: int) -> int:
-    return (1 << (bits - 1)) - 1
-
-
-def allocate_group_bits(weights, avg_bits: float = 4.0, model: str = "mse", widths=GROUP_BITS) -> tuple:
-    """Bit allocation over the 64-channel groups of a boundary: every group starts at the narrowest width and the
-    budget ``avg_bits * G`` bits goes, one step up the width ladder at a time, to the step with the largest error
-    reduction per bit.  Error models of a group g quantized at b bits (max-abs scale, step amax / qmax_b):
-
-    * ``"mse"``: the expected squared first-order output change, W_g / (12 qmax_b^2) with W_g the group's
-      quantization sensitivity sum_t max_c |x_tc|^2 sum_c dx_tc^2 (``ops.reference.group_sens``: a rounding error
-      uniform in +-step/2 per channel, independent across channels, propagated through the gradient dx).  The
-      error falls 4-9x per added bit, so a group gets a wider code only where its sensitivity is that much larger
-      than the others' - the outlier-heavy groups;
-    * ``"linear"``: R_g / qmax_b with R_g the LRP relevance sum |x dx| (the round-3 allocator: error ~ sum |dx|
-      step / 2), only on the widths 2 / 4 / 8.
-
-    The error reductions per bit fall along the ladder (convex), so the greedy allocation is optimal for the
-    model.  Equal weights give the uniform plan."""
-    w = [max(float(r), 0.0) for r in weights]
-    G = len(w)
-    if not any(w):
-        w = [1.0] * G
-    if model == "linear":
-        ladder = (2, 4, 8)
-        err = {b: 1.0 / _qmax(b) for b in ladder}
-    elif model == "mse":
-        ladder = tuple(sorted(widths))
-        err = {b: 1.0 / _qmax(b) ** 2 for b in ladder}
-    else:
-        raise ValueError(f"unknown allocation model {model!r} (mse | linear)")
-    nxt = {ladder[i]: ladder[i + 1] for i in range(len(ladder) - 1)}
-    bits = [ladder[0]] * G
-    budget = int(round(avg_bits * G)) - ladder[0] * G
-    while budget > 0:
-        best, best_gain = -1, 0.0
-        for g in range(G):
-            b = bits[g]
-            if b not in nxt:
-                continue
-            nb = nxt[b]
-            cost = nb - b
-            if cost > budget:
-                continue
-            gain = w[g] * (err[b] - err[nb]) / cost
-            if gain > best_gain or (gain == best_gain and best >= 0 and w[g] > w[best]):
-                best, best_gain = g, gain
-        if best < 0:
-            break
-        budget -= nxt[bits[best]] - bits[best]
-        bits[best] = nxt[bits[best]]
-    return tuple(bits)
-
-
-def load_group_tables(relevance_path: str):
-    """``channel_group_relevance.json`` and, when the relevance pass wrote it beside, the sensitivity table
-    ``channel_group_sensitivity.json`` -> {"relevance": tensor, "sensitivity": tensor or None}."""
-    import json
-    import os
-    with open(relevance_path) as f:
-        rel = torch.tensor(json.load(f), dtype=torch.float32)
-    sp = os.path.join(os.path.dirname(os.path.abspath(relevance_path)), "channel_group_sensitivity.json")
-    sens = None
-    if os.path.exists(sp):
-        with open(sp) as f:
-            sens = torch.tensor(json.load(f), dtype=torch.float32)
-    return {"relevance": rel, "sensitivity": sens}
-
-
 def get_codec(name: str) -> CodecSpec:
     if name not in CODECS:
         raise KeyError(f"unknown codec {name!r}; known: {sorted(CODECS)}")
@@ -218,10 +121,12 @@ def _a16(n: int) -> int:
 
 
 def _row_bytes(fmt: int, H: int, plan=None) -> int:
-    if fmt in GRP_FORMATS:   # codes of every group (8 * bits bytes), then one fp32 scale per group
-        return sum(8 * b for b in plan) + 4 * len(plan)
-    return {FMT_BF16: 2 * H, FMT_INT8: H, FMT_INT4: H // 2, FMT_INT2: H // 4, FMT_F32: 4 * H,
-            FMT_MXFP4: H // 2 + H // 32, FMT_MXFP8: H + H // 32}[fmt]
+    return ROW_FORMATS[fmt].row_bytes(H, plan)
+
+
+def _scale_shape(mode: int, B: int, S: int, H: int):
+    """Shape of the message's fp32 scale section (None: no section)."""
+    return {SC_TOKEN: (B, S), SC_WINDOW: (B,), SC_CHANNEL: (B, H), SC_NONE: None}[mode]
 
 
 @dataclass(frozen=True)
@@ -254,8 +159,7 @@ class Layout:
         """Bytes of the message proper: ``total`` for fixed k; for variable k with ``k_total`` lo rows in all."""
         if not self.kvar:
             return self.total
-        return self.off_lo + _a16(k_total * self.row_bytes(self.lo_fmt)) + \
-            (self.B * self.S - k_total) * self.row_bytes(self.hi_fmt)
+        return self.hi_offset(k_total) + (self.B * self.S - k_total) * self.row_bytes(self.hi_fmt)
 
     def hi_offset(self, k_total: int) -> int:
         return self.off_hi if not self.kvar else self.off_lo + _a16(k_total * self.row_bytes(self.lo_fmt))
@@ -294,7 +198,7 @@ def layout(spec: CodecSpec, B: int, S: int, H: int, k: int, dtype: torch.dtype =
     rb = lambda f: _row_bytes(f, H, plan)  # noqa: E731
     mw = 2 * ((S + 63) // 64)
     off_mask = 32
-    n_scale = {SC_TOKEN: B * S, SC_WINDOW: B, SC_CHANNEL: B * H, SC_NONE: 0}[spec.scale_mode]
+    n_scale = math.prod(_scale_shape(spec.scale_mode, B, S, H) or (0,))
     # the group plan section (one byte per group) follows the mask (and the k vector)
     plan_bytes = _a16(len(plan)) if plan is not None else 0
     if kvar:
@@ -476,7 +380,7 @@ def _mx_pack(rows: torch.Tensor, fmt: int) -> torch.Tensor:
 
 
 def _mx_unpack(b: torch.Tensor, fmt: int, n: int, H: int) -> torch.Tensor:
-    r = b.reshape(n, _row_bytes(fmt, H))
+    r = b.reshape(n, -1)
     nc = H // 2 if fmt == FMT_MXFP4 else H
     codes, sb = r[:, :nc], r[:, nc:].to(torch.int64)
     if fmt == FMT_MXFP4:
@@ -545,25 +449,13 @@ def _grp_pack(rows: torch.Tensor, plan, rot: bool = False) -> torch.Tensor:
     return torch.cat(parts + [sc], 1).reshape(-1)
 
 
-def _grp_unpack(b: torch.Tensor, plan, n: int, H: int) -> torch.Tensor:
-    r = b.reshape(n, _row_bytes(FMT_GRP, H, plan))
-    cb = sum(8 * x for x in plan)
-    sc = r[:, cb:].contiguous().view(torch.float32).reshape(n, len(plan))
-    out, off = [], 0
-    for g, bits in enumerate(plan):
-        nb = 8 * bits
-        q = _grp_bits_unpack(r[:, off:off + nb].contiguous(), bits)
-        out.append(q * sc[:, g:g + 1])
-        off += nb
-    return torch.cat(out, 1)
-
-
-def _grpr_unpack(b: torch.Tensor, msg_plan, plan, n: int, H: int) -> torch.Tensor:
-    """FMT_GRPR rows -> fp32 [n, H]: the group's integer codes go through the butterflies as integers (exact) and one
-    multiply by s / 8 gives x' = H64 q s / 8 (csrc/codec.hip grp_unpack8_rot).  The row stride comes from the codec's
-    plan, the widths from the MESSAGE's plan bytes as on the GPU: a width outside GROUP_BITS, or a group stream
-    reaching past the row's code bytes, gives NaN from that group on (invalid widths count 0 bytes in the offset)."""
-    r = b.reshape(n, _row_bytes(FMT_GRPR, H, plan))
+def _grp_unpack(b: torch.Tensor, msg_plan, plan, n: int, rot: bool = False) -> torch.Tensor:
+    """FMT_GRP / FMT_GRPR rows -> fp32 [n, H].  The row stride comes from the codec's plan, the widths from the
+    MESSAGE's plan bytes as on the GPU (csrc/codec.hip grp_walk): a width outside GROUP_BITS, or a group stream
+    reaching past the row's code bytes, gives NaN from that group on (invalid widths count 0 bytes in the offset).
+    ``rot`` (FMT_GRPR): the group's integer codes go through the butterflies as integers (exact) and one multiply by
+    s / 8 gives x' = H64 q s / 8."""
+    r = b.reshape(n, -1)
     cb = sum(8 * x for x in plan)
     sc = r[:, cb:].contiguous().view(torch.float32).reshape(n, len(plan))
     out, off, bad = [], 0, False
@@ -573,138 +465,148 @@ def _grpr_unpack(b: torch.Tensor, msg_plan, plan, n: int, H: int) -> torch.Tenso
         if bad:
             out.append(torch.full((n, GROUP), float("nan")))
         else:
-            q = _grp_bits_unpack(r[:, off:off + 8 * bits].contiguous(), bits).to(torch.int64)
-            out.append(_wht64(q).float() * (sc[:, g:g + 1] * 0.125))
+            q = _grp_bits_unpack(r[:, off:off + 8 * bits].contiguous(), bits)
+            out.append(_wht64(q.to(torch.int64)).float() * (sc[:, g:g + 1] * 0.125) if rot else q * sc[:, g:g + 1])
         off += 8 * bits if ok else 0
     return torch.cat(out, 1)
+
+
+def _bytes(t: torch.Tensor) -> torch.Tensor:
+    return t.contiguous().view(torch.uint8).reshape(-1)
+
+
+@dataclass(frozen=True)
+class RowCtx:
+    """What a row format's CPU pack / unpack may need beyond the rows of one class."""
+    H: int
+    plan: tuple | None                 # the codec's group bit plan (row stride)
+    msg_plan: list | None              # the plan bytes as the message holds them (widths, when decoding)
+    spec: CodecSpec
+    is_lo: bool
+    scale_row: torch.Tensor | None     # [n] per-row scale of the class's rows (token / window modes)
+    ch_scale: torch.Tensor | None      # [n, H] per-channel scale of the class's rows (channel mode)
+
+
+@dataclass(frozen=True)
+class RowFormat:
+    """One row format of the wire."""
+    row_bytes: Callable[[int, tuple | None], int]                   # (H, plan) -> bytes of one row
+    self_scaled: bool          # no entry in the message's scale section (csrc/codec.hip SELF_SCALED)
+    pack: Callable[[torch.Tensor, RowCtx], torch.Tensor]            # (fp32 rows [n, H], ctx) -> the rows' bytes
+    unpack: Callable[[torch.Tensor, int, RowCtx], torch.Tensor]     # (bytes, n, ctx) -> fp32 rows [n, H]
+
+
+def _int_rows(fmt: int, per_byte: int) -> RowFormat:
+    def pack(rows, c):
+        return _pack_rows(_qcodes(rows, c.spec, c.is_lo, c.scale_row, c.ch_scale), fmt)
+
+    def unpack(raw, n, c):
+        return _dequant(_unpack_rows(raw, fmt, n, c.H), c.spec, c.is_lo, c.scale_row, c.ch_scale)
+    return RowFormat(lambda H, plan: H // per_byte, False, pack, unpack)
+
+
+def _mx_rows(fmt: int, per_byte: int) -> RowFormat:    # codes, then one E8M0 byte per 32 channels
+    return RowFormat(lambda H, plan: H // per_byte + H // 32, True,
+                     lambda rows, c: _mx_pack(rows, fmt), lambda raw, n, c: _mx_unpack(raw, fmt, n, c.H))
+
+
+def _grp_rows(rot: bool) -> RowFormat:   # codes of every group (8 * bits bytes), then one fp32 scale per group
+    return RowFormat(lambda H, plan: sum(8 * b for b in plan) + 4 * len(plan), True,
+                     lambda rows, c: _grp_pack(rows, c.plan, rot),
+                     lambda raw, n, c: _grp_unpack(raw, c.msg_plan, c.plan, n, rot))
+
+
+ROW_FORMATS = {
+    FMT_BF16: RowFormat(lambda H, plan: 2 * H, True, lambda rows, c: _bytes(rows.to(torch.bfloat16)),
+                        lambda raw, n, c: raw.view(torch.bfloat16).reshape(n, c.H).float()),
+    FMT_F32: RowFormat(lambda H, plan: 4 * H, True, lambda rows, c: _bytes(rows),
+                       lambda raw, n, c: raw.view(torch.float32).reshape(n, c.H)),
+    FMT_INT8: _int_rows(FMT_INT8, 1), FMT_INT4: _int_rows(FMT_INT4, 2), FMT_INT2: _int_rows(FMT_INT2, 4),
+    FMT_MXFP4: _mx_rows(FMT_MXFP4, 2), FMT_MXFP8: _mx_rows(FMT_MXFP8, 1),
+    FMT_GRP: _grp_rows(False), FMT_GRPR: _grp_rows(True),
+}
 
 
 def _header(spec: CodecSpec, L: Layout) -> torch.Tensor:
     return torch.tensor([MAGIC, VERSION, spec.cid, L.B, L.S, L.H, -1 if L.kvar else L.k, L.hi_fmt], dtype=torch.int32)
 
 
-def _encode_cpu(x, spec, L, lo_mask):
-    B, S, H, k = L.B, L.S, L.H, L.k
-    msg = torch.zeros(L.total, dtype=torch.uint8)
-    msg[:32] = _header(spec, L).view(torch.uint8)
-    mw_bytes = _mask_words(lo_mask, L.mw).view(torch.uint8).reshape(-1)
-    msg[L.off_mask:L.off_mask + mw_bytes.numel()] = mw_bytes
+def _classes(spec, L, lo_mask, scales, msg_plan):
+    """Per class with rows, hi first: (row format, selection [B, S], message offset, RowCtx of the selection)."""
     kt = int(lo_mask.sum())
-    if L.kvar:
-        kv = lo_mask.sum(1).to(torch.int32).contiguous().view(torch.uint8)
-        msg[L.off_kvec:L.off_kvec + kv.numel()] = kv
-    if L.plan is not None:
-        msg[L.off_plan:L.off_plan + len(L.plan)] = torch.tensor(L.plan, dtype=torch.uint8)
-    xf = x.float().reshape(B, S, H)
-    # statistics
-    scales = None
-    ch = None
-    if spec.scale_mode == SC_TOKEN:
-        scales = torch.zeros(B, S)
-        for is_lo, fmt, qmax in ((False, L.hi_fmt, spec.qmax_hi), (True, L.lo_fmt, spec.qmax_lo)):
-            if fmt in (FMT_BF16, FMT_F32) or fmt in GRP_FORMATS or fmt in MX_FORMATS:
-                continue
-            sel = lo_mask if is_lo else ~lo_mask
-            am = xf.abs().amax(-1)
-            scales = torch.where(sel, am / float(qmax), scales)
-        msg[L.off_scale:L.off_scale + B * S * 4] = scales.reshape(-1).view(torch.uint8)
-    elif spec.scale_mode == SC_WINDOW:
-        am = torch.where(lo_mask[..., None], xf.abs(), torch.zeros_like(xf)).amax(dim=(1, 2))
-        scales = am
-        msg[L.off_scale:L.off_scale + B * 4] = am.view(torch.uint8)
-    elif spec.scale_mode == SC_CHANNEL:
-        ch = xf.abs().amax(1) if spec.ch_kind == CH_MAXABS else xf.mean(1) + 1e-8   # [B, H]
-        msg[L.off_scale:L.off_scale + B * H * 4] = ch.reshape(-1).contiguous().view(torch.uint8)
-    # rows
-    for is_lo in (False, True):
-        fmt = L.lo_fmt if is_lo else L.hi_fmt
+    for is_lo, fmt in ((False, L.hi_fmt), (True, L.lo_fmt)):
         sel = lo_mask if is_lo else ~lo_mask
         if not bool(sel.any()):
             continue
-        rows = xf[sel]                                      # [n, H] in window/token order
-        off = L.off_lo if is_lo else L.hi_offset(kt)
-        if fmt == FMT_F32:
-            data = rows.contiguous().view(torch.uint8).reshape(-1)
-        elif fmt == FMT_BF16:
-            data = rows.to(torch.bfloat16).contiguous().view(torch.uint8).reshape(-1)
-        elif fmt in MX_FORMATS:
-            data = _mx_pack(rows, fmt)
-        elif fmt == FMT_GRP:
-            data = _grp_pack(rows, L.plan)
-        elif fmt == FMT_GRPR:
-            data = _grp_pack(rows, L.plan, rot=True)
-        else:
-            if spec.scale_mode == SC_TOKEN:
-                srow = scales[sel]
-                q = _qcodes(rows, spec, is_lo, srow, None)
-            elif spec.scale_mode == SC_WINDOW:
-                srow = scales.view(B, 1).expand(B, S)[sel]
-                q = _qcodes(rows, spec, is_lo, srow, None)
-            else:
-                chr_ = ch.view(B, 1, H).expand(B, S, H)[sel]
-                q = _qcodes(rows, spec, is_lo, None, chr_)
-            data = _pack_rows(q, fmt)
+        srow = ch = None
+        if spec.scale_mode == SC_CHANNEL:
+            ch = scales.view(L.B, 1, L.H).expand(L.B, L.S, L.H)[sel]
+        elif spec.scale_mode != SC_NONE:
+            srow = (scales if spec.scale_mode == SC_TOKEN else scales.view(L.B, 1).expand(L.B, L.S))[sel]
+        yield (ROW_FORMATS[fmt], sel, L.off_lo if is_lo else L.hi_offset(kt),
+               RowCtx(L.H, L.plan, msg_plan, spec, is_lo, srow, ch))
+
+
+def _encode_cpu(x, spec, L, lo_mask):
+    B, S, H = L.B, L.S, L.H
+    msg = torch.zeros(L.total, dtype=torch.uint8)
+
+    def put(off, t):
+        data = _bytes(t)
         msg[off:off + data.numel()] = data
+
+    put(0, _header(spec, L))
+    put(L.off_mask, _mask_words(lo_mask, L.mw))
+    if L.kvar:
+        put(L.off_kvec, lo_mask.sum(1).to(torch.int32))
+    if L.plan is not None:
+        put(L.off_plan, torch.tensor(L.plan, dtype=torch.uint8))
+    xf = x.float().reshape(B, S, H)
+    # statistics
+    scales = None
+    if spec.scale_mode == SC_TOKEN:
+        scales = torch.zeros(B, S)
+        for is_lo, fmt, qmax in ((False, L.hi_fmt, spec.qmax_hi), (True, L.lo_fmt, spec.qmax_lo)):
+            if not ROW_FORMATS[fmt].self_scaled:
+                scales = torch.where(lo_mask if is_lo else ~lo_mask, xf.abs().amax(-1) / float(qmax), scales)
+    elif spec.scale_mode == SC_WINDOW:
+        scales = torch.where(lo_mask[..., None], xf.abs(), torch.zeros_like(xf)).amax(dim=(1, 2))
+    elif spec.scale_mode == SC_CHANNEL:
+        scales = xf.abs().amax(1) if spec.ch_kind == CH_MAXABS else xf.mean(1) + 1e-8   # [B, H]
+    if scales is not None:
+        put(L.off_scale, scales)
+    # rows, in window/token order
+    for rf, sel, off, c in _classes(spec, L, lo_mask, scales, L.plan):
+        put(off, rf.pack(xf[sel], c))
     return msg
 
 
 def _decode_cpu(msg, spec, L, dtype):
-    B, S, H, k = L.B, L.S, L.H, L.k
+    B, S, H = L.B, L.S, L.H
     words = msg[L.off_mask:L.off_mask + B * L.mw * 4].view(torch.int32).reshape(B, L.mw)
     lo_mask = _words_to_mask(words, S)
     out = torch.empty(B, S, H, dtype=torch.float32)
-    scales = None
-    ch = None
-    if spec.scale_mode == SC_TOKEN:
-        scales = msg[L.off_scale:L.off_scale + B * S * 4].view(torch.float32).reshape(B, S)
-    elif spec.scale_mode == SC_WINDOW:
-        scales = msg[L.off_scale:L.off_scale + B * 4].view(torch.float32)
-    elif spec.scale_mode == SC_CHANNEL:
-        ch = msg[L.off_scale:L.off_scale + B * H * 4].view(torch.float32).reshape(B, H)
-    kt = int(lo_mask.sum())
-    for is_lo in (False, True):
-        fmt = L.lo_fmt if is_lo else L.hi_fmt
-        sel = lo_mask if is_lo else ~lo_mask
+    shape = _scale_shape(spec.scale_mode, B, S, H)
+    scales = None if shape is None else \
+        msg[L.off_scale:L.off_scale + 4 * math.prod(shape)].view(torch.float32).reshape(shape)
+    msg_plan = None if L.plan is None else msg[L.off_plan:L.off_plan + len(L.plan)].tolist()
+    for rf, sel, off, c in _classes(spec, L, lo_mask, scales, msg_plan):
         n = int(sel.sum())
-        if n == 0:
-            continue
-        off = L.off_lo if is_lo else L.hi_offset(kt)
-        nb = n * L.row_bytes(fmt)
-        raw = msg[off:off + nb]
-        if fmt == FMT_F32:
-            rows = raw.view(torch.float32).reshape(n, H)
-        elif fmt == FMT_BF16:
-            rows = raw.view(torch.bfloat16).reshape(n, H).float()
-        elif fmt in MX_FORMATS:
-            rows = _mx_unpack(raw, fmt, n, H)
-        elif fmt == FMT_GRP:
-            rows = _grp_unpack(raw, L.plan, n, H)
-        elif fmt == FMT_GRPR:
-            rows = _grpr_unpack(raw, msg[L.off_plan:L.off_plan + len(L.plan)].tolist(), L.plan, n, H)
-        else:
-            q = _unpack_rows(raw, fmt, n, H)
-            if spec.scale_mode == SC_TOKEN:
-                rows = _dequant(q, spec, is_lo, scales[sel], None)
-            elif spec.scale_mode == SC_WINDOW:
-                rows = _dequant(q, spec, is_lo, scales.view(B, 1).expand(B, S)[sel], None)
-            else:
-                rows = _dequant(q, spec, is_lo, None, ch.view(B, 1, H).expand(B, S, H)[sel])
-        out[sel] = rows
+        out[sel] = rf.unpack(msg[off:off + n * rf.row_bytes(H, L.plan)], n, c)
     return out.reshape(B * S, H).to(dtype)
 
 
 # --------------------------------------------------------------------------------------------
 # GPU implementation
-_HDR_CACHE: dict = {}
+_DEV_CONSTS: dict = {}
 
 
-def _gpu_header(spec, L, device):
-    key = (spec.cid, L, device)
-    h = _HDR_CACHE.get(key)
-    if h is None:
-        h = _header(spec, L).view(torch.uint8).to(device)
-        _HDR_CACHE[key] = h
-    return h
+def _dev_const(key, device, make):
+    """A small constant tensor (header, plan bytes) on ``device``, uploaded once."""
+    t = _DEV_CONSTS.get((key, device))
+    if t is None:
+        t = _DEV_CONSTS[(key, device)] = make().to(device)
+    return t
 
 
 def _args(spec, L):
@@ -713,26 +615,15 @@ def _args(spec, L):
             L.hi_fmt, L.lo_fmt, spec.scale_mode, spec.qmax_hi, spec.qmax_lo, spec.ch_kind, gcb)
 
 
-_PLAN_CACHE: dict = {}
-
-
-def _gpu_plan(L, device):
-    key = (L.plan, device)
-    t = _PLAN_CACHE.get(key)
-    if t is None:
-        t = torch.tensor(L.plan, dtype=torch.uint8).to(device)
-        _PLAN_CACHE[key] = t
-    return t
-
-
 def _encode_gpu(x, spec, L, imp, msg, mass=0.0):
     if x.dtype not in (torch.bfloat16, torch.float32):
         raise TypeError("GPU boundary codec expects bf16 or fp32 activations")
     xf32 = int(x.dtype == torch.float32)
     st = stream()
-    msg[:32].copy_(_gpu_header(spec, L, x.device))
+    msg[:32].copy_(_dev_const(("header", spec.cid, L), x.device, lambda: _header(spec, L).view(torch.uint8)))
     if L.plan is not None:
-        msg[L.off_plan:L.off_plan + len(L.plan)].copy_(_gpu_plan(L, x.device))
+        msg[L.off_plan:L.off_plan + len(L.plan)].copy_(
+            _dev_const(("plan", L.plan), x.device, lambda: torch.tensor(L.plan, dtype=torch.uint8)))
     if L.kvar:
         if imp is None:
             raise ValueError("top-rho selection needs token importance")
@@ -781,37 +672,32 @@ def encode(x: torch.Tensor, spec: CodecSpec, B: int, S: int, ratio: float = 0.0,
     directly).  ``"top_rho"``: every window keeps its shortest descending-importance prefix reaching mass
     ``1 - ratio`` and quantizes the rest (per-window k, variable-k message)."""
     H = x.shape[-1]
-    if uses_kvar(spec, selection):
-        mass = 1.0 - float(ratio)
+    kvar, mass = uses_kvar(spec, selection), 1.0 - float(ratio)
+    if kvar:
         if importance is None:
             if mass > 0:
                 raise ValueError("top-rho selection needs token importance")
             # ratio >= 1: keep mass <= 0 keeps nothing for any importance (every window all lo, k = S)
             importance = torch.zeros(B, S, dtype=torch.float32, device=x.device)
         L = layout(spec, B, S, H, -1, x.dtype, kvar=True)
-        if x.is_cuda:
-            if out is None:
-                out = torch.zeros(L.total, dtype=torch.uint8, device=x.device)
-            return _encode_gpu(x.contiguous(), spec, L, importance, out, mass), L
-        lo = select_mask(importance, top_rho_k(importance, mass))
-        msg = _encode_cpu(x, spec, L, lo)
-        if out is not None:
-            out.copy_(msg)
-            return out, L
-        return msg, L
-    k = num_lo(spec, ratio, S) if k is None else (k if spec.uses_ratio else 0)
-    L = layout(spec, B, S, H, k, x.dtype)
+    else:
+        k = num_lo(spec, ratio, S) if k is None else (k if spec.uses_ratio else 0)
+        L = layout(spec, B, S, H, k, x.dtype)
     if x.is_cuda:
         if out is None:  # zero-filled so the 16-byte section padding is deterministic on the wire
             out = torch.zeros(L.total, dtype=torch.uint8, device=x.device)
-        return _encode_gpu(x.contiguous(), spec, L, importance, out), L
-    lo = select_mask(importance.float(), k) if (0 < k < S) else \
-        torch.full((B, S), k >= S and k > 0, dtype=torch.bool)
+        return _encode_gpu(x.contiguous(), spec, L, importance, out, mass if kvar else 0.0), L
+    if kvar:
+        lo = select_mask(importance, top_rho_k(importance, mass))
+    elif 0 < k < S:
+        lo = select_mask(importance.float(), k)
+    else:
+        lo = torch.full((B, S), k >= S and k > 0, dtype=torch.bool)
     msg = _encode_cpu(x, spec, L, lo)
-    if out is not None:
-        out.copy_(msg)
-        return out, L
-    return msg, L
+    if out is None:
+        return msg, L
+    out.copy_(msg)
+    return out, L
 
 
 def decode(msg: torch.Tensor, spec: CodecSpec, L: Layout, dtype=torch.bfloat16, out=None) -> torch.Tensor:

@@ -168,7 +168,7 @@ class SweepEngine:
         if not C.wire.needs_plan(spec):
             return spec
         G = self.m.cfg.hidden_size // C.wire.GROUP
-        return C.wire.with_plan(spec, C.wire.boundary_group_plan(self.sc.group_relevance, L, G,
+        return C.wire.with_plan(spec, C.plan.boundary_group_plan(self.sc.group_relevance, L, G,
                                                                  self.sc.group_avg_bits))
 
     def _k(self, ratio, S, spec=None):

@@ -43,7 +43,7 @@ class BoundaryConfig:
     head_weights: torch.Tensor | None = None
     selection: str = "ratio"      # "ratio": int(ratio*S) least important; "top_rho": keep mass 1 - ratio
     # head-group codecs (rgroup, rgroup_rot, mixed_rgroup_int8): the relevance pass's channel-group tables of the
-    # residual stream entering each layer - {"relevance", "sensitivity"} (codec.wire.load_group_tables) or a plain
+    # residual stream entering each layer - {"relevance", "sensitivity"} (codec.plan.load_group_tables) or a plain
     # [layers][H / 64] relevance list - and the average bits per channel; without a table every group gets the same
     # width
     group_relevance: object = None
@@ -60,7 +60,7 @@ class BoundaryConfig:
         if boundary is None or not C.wire.needs_plan(spec):
             return spec
         G = hidden // C.wire.GROUP
-        return C.wire.with_plan(spec, C.wire.boundary_group_plan(self.group_relevance, boundary, G,
+        return C.wire.with_plan(spec, C.plan.boundary_group_plan(self.group_relevance, boundary, G,
                                                                  self.group_avg_bits))
 
     @property

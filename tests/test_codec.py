@@ -261,7 +261,8 @@ def test_mx_codecs_error_and_bytes(codec):
 
 @pytest.mark.parametrize("model", ["linear", "mse"])
 def test_group_bits_allocation(model):
-    from llm_inference_in_distributed_edge_networks_amd.codec.wire import GROUP_BITS, allocate_group_bits
+    from llm_inference_in_distributed_edge_networks_amd.codec.plan import allocate_group_bits
+    from llm_inference_in_distributed_edge_networks_amd.codec.wire import GROUP_BITS
     rel = [0.30, 0.01, 0.20, 0.02, 0.25, 0.01, 0.10, 0.11]
     bits = allocate_group_bits(rel, 4.0, model=model)
     assert sum(bits) == 4 * len(rel) and set(bits) <= ({2, 4, 8} if model == "linear" else set(GROUP_BITS))
@@ -279,7 +280,8 @@ def test_group_bits_mse_model():
     (checked against every plan of two groups), and a 1.2x spread - the surrogate model's relevance spread - stays
     uniform at 4 bits while an outlier-sized (100x) group takes bits from the others."""
     import itertools
-    from llm_inference_in_distributed_edge_networks_amd.codec.wire import GROUP_BITS, allocate_group_bits
+    from llm_inference_in_distributed_edge_networks_amd.codec.plan import allocate_group_bits
+    from llm_inference_in_distributed_edge_networks_amd.codec.wire import GROUP_BITS
     q = {b: (1 << (b - 1)) - 1 for b in GROUP_BITS}
     assert allocate_group_bits([1.0, 1.2, 1.1, 1.0], 4.0) == (4, 4, 4, 4)
     hot = allocate_group_bits([100.0, 1.0, 1.0, 1.0], 4.0)
@@ -295,7 +297,7 @@ def test_group_bits_mse_model():
 def test_boundary_group_plan_tables(tmp_path):
     """A sensitivity table beside the relevance table switches the plan to the MSE allocation over it."""
     import json
-    from llm_inference_in_distributed_edge_networks_amd.codec.wire import (allocate_group_bits, boundary_group_plan,
+    from llm_inference_in_distributed_edge_networks_amd.codec.plan import (allocate_group_bits, boundary_group_plan,
                                                                             load_group_tables)
     rel = [[1.0, 1.1, 0.9, 1.0]] * 3
     sens = [[1.0, 1.0, 1.0, 1.0], [80.0, 1.0, 1.0, 1.0], [1.0, 1.0, 1.0, 90.0]]
@@ -313,7 +315,7 @@ def test_boundary_group_plan_tables(tmp_path):
 def test_boundary_group_relevance_rows():
     """Boundary after layer L -> the table row of the stream entering L + 1; after the LAST layer (the reference's
     layer 23 of 24) the table's last row - the quality sweep at boundary 23 indexed past the table before."""
-    from llm_inference_in_distributed_edge_networks_amd.codec.wire import boundary_group_relevance
+    from llm_inference_in_distributed_edge_networks_amd.codec.plan import boundary_group_relevance
     table = [[float(10 * i + g) for g in range(3)] for i in range(24)]
     assert boundary_group_relevance(table, 11, 3) == table[12]
     assert boundary_group_relevance(table, 22, 3) == table[23]

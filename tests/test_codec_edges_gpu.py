@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 import torch
 
+import test_codec_digests as D
 import test_codec_edges as E
 from llm_inference_in_distributed_edge_networks_amd import codec as C
 from llm_inference_in_distributed_edge_networks_amd.codec import wire as W
@@ -160,3 +161,14 @@ def test_nonfinite(name, placement, B, S, H):
     assert np.array_equal(m_gpu.numpy()[~w0], m_cpu.numpy()[~w0])
     if case.spec.lo_fmt in W.MX_FORMATS or case.spec.hi_fmt in W.MX_FORMATS:
         E.check_mx_nonfinite(case, m_gpu, L, y_gpu, y_clean)
+
+
+DIGEST_CASES = [c for c in D.cases() if c[3] == "f32" and c[1] != "channel_1_mean"]
+
+
+@pytest.mark.parametrize("key,name,spec,dn,ratio,sel", DIGEST_CASES, ids=[c[0] for c in DIGEST_CASES])
+def test_gpu_digest(key, name, spec, dn, ratio, sel):
+    """The GPU's message and fp32 decode of the fp32-activation cases of tests/golden/codec_digests.json: the bytes the
+    CPU codec emitted before it and the kernels were restructured together.  channel_1_mean (a channel mean:
+    summation order) is not compared."""
+    assert D.run_case(spec, dn, ratio, sel, DEV) == D.fixture()[key]

@@ -131,12 +131,13 @@ def test_outlier_behaviour():
 
 
 @pytest.mark.parametrize("bad", [0, 7, 255])
-def test_corrupt_plan_decodes_to_nan_from_that_group(bad):
-    """The CPU decoder reads the widths from the message's plan bytes as the GPU does: a width outside GROUP_BITS
-    gives NaN from that group on and leaves the groups before it intact."""
+@pytest.mark.parametrize("name", ["rgroup", "rgroup_rot"])
+def test_corrupt_plan_decodes_to_nan_from_that_group(name, bad):
+    """The CPU decoder reads the widths from the message's plan bytes as the GPU does, for plain and rotated head-group
+    rows: a width outside GROUP_BITS gives NaN from that group on and leaves the groups before it intact."""
     B, S, H = 2, 16, 512
     x = torch.randn(B * S, H, generator=torch.Generator().manual_seed(4))
-    spec = rot((4,) * 8)
+    spec = W.with_plan(C.get_codec(name), (4,) * 8)
     msg, L = C.encode(x, spec, B, S)
     good = C.decode(msg, spec, L, torch.float32)
     assert torch.isfinite(good).all()

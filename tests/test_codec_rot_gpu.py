@@ -6,6 +6,7 @@ import pytest
 import torch
 
 from llm_inference_in_distributed_edge_networks_amd import codec as C
+from llm_inference_in_distributed_edge_networks_amd.codec import plan as P
 from llm_inference_in_distributed_edge_networks_amd.codec import wire as W
 
 pytestmark = pytest.mark.gpu
@@ -24,7 +25,7 @@ def plan_of(kind, H):
     if kind == "all_widths":
         return tuple(W.GROUP_BITS[g % len(W.GROUP_BITS)] for g in range(G))
     # a few dominant groups: the MSE allocation is non-uniform (one group: 4 bits)
-    return W.allocate_group_bits([100.0 if g % 5 == 0 else 1.0 for g in range(G)], 4.0, model="mse")
+    return P.allocate_group_bits([100.0 if g % 5 == 0 else 1.0 for g in range(G)], 4.0, model="mse")
 
 
 def spec_of(kind, H):
@@ -91,7 +92,9 @@ def test_gpu_rejects_corrupt_plan(bad):
     torch.cuda.synchronize()
     assert torch.equal(y[:, :192], y_cpu[:, :192])
     assert torch.isnan(y[:, 192:]).all()
-    assert torch.equal(torch.isnan(y), torch.isnan(C.decode(msg, spec, L, torch.float32)))
+    y_bad = C.decode(msg, spec, L, torch.float32)          # the CPU decode of the same corrupted bytes
+    assert torch.equal(torch.isnan(y), torch.isnan(y_bad))
+    assert torch.equal(y[~torch.isnan(y)], y_bad[~torch.isnan(y_bad)])
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])

@@ -107,8 +107,8 @@ def test_rgroup_sweep_equals_pipeline_with_relevance_table(tmp_path):
     from llm_inference_in_distributed_edge_networks_amd.models import TINY_QWEN2
     G = TINY_QWEN2.hidden_size // 64
     rel = [[(10.0 if g == G - 1 else 0.05) * (1 + l) for g in range(G)] for l in range(TINY_QWEN2.num_layers + 1)]
-    from llm_inference_in_distributed_edge_networks_amd.codec import wire
-    assert wire.allocate_group_bits(rel[2], 4.0) != wire.allocate_group_bits([1.0] * G, 4.0)   # the table matters
+    from llm_inference_in_distributed_edge_networks_amd.codec import plan
+    assert plan.allocate_group_bits(rel[2], 4.0) != plan.allocate_group_bits([1.0] * G, 4.0)   # the table matters
     tab = tmp_path / "grel.json"
     tab.write_text(json.dumps(rel))
     common = {"model": "tiny-qwen2", "max_length": 128, "ratios": [0.5, 1.0], "methods": ["last_row"],

@@ -428,7 +428,8 @@ def test_group_codec_gpu_equals_cpu(name, dtype, plan):
     """Head-group rows with a non-uniform plan (the round-3 linear allocation on 2 / 4 / 8 bits, the MSE allocation,
     and every width 2 / 3 / 4 / 5 / 6 / 8 in one row): GPU message bytes == CPU oracle bytes (fp32 activations; bf16
     activations: same bytes from the bf16-rounded input), decode equal."""
-    from llm_inference_in_distributed_edge_networks_amd.codec.wire import GROUP_BITS, allocate_group_bits, with_plan
+    from llm_inference_in_distributed_edge_networks_amd.codec.plan import allocate_group_bits
+    from llm_inference_in_distributed_edge_networks_amd.codec.wire import GROUP_BITS, with_plan
     B, S, H = 3, 200, 896
     x = (rnd(B * S, H, seed=60) * 2).to(dtype)
     x[:, 128:192] *= 30
@@ -470,3 +471,6 @@ def test_group_codec_gpu_rejects_corrupt_plan(bad):
     torch.cuda.synchronize()
     assert torch.equal(y[:, :192], good[:, :192])          # groups 0-2: before the corrupt width
     assert torch.isnan(y[:, 192:]).all()                   # group 3 and every group after it
+    y_cpu = C.decode(msg.cpu(), spec, L, torch.float32)    # the CPU decoder reads the message's plan bytes too
+    assert torch.equal(torch.isnan(y), torch.isnan(y_cpu))
+    assert torch.equal(y[~torch.isnan(y)], y_cpu[~torch.isnan(y_cpu)])

@@ -11,7 +11,7 @@ message the RCCL transport carries) on the byte-level Qwen2 trained by ``tools/t
   the LRP head table), plus ``last_row`` at every depth so the compounding is visible on one method;
 * codecs: the config's codec, the reference Q1 (``ref_int4_global``) at every boundary, and for config 5 the
   head-group codec with allocated plans against the same codec with uniform plans (same bits): "sens" = the MSE
-  allocation over the groups' quantization sensitivity on the widths 2-8 (``codec.wire.allocate_group_bits``), "rel"
+  allocation over the groups' quantization sensitivity on the widths 2-8 (``codec.plan.allocate_group_bits``), "rel"
   = round 3's first-order allocation over the LRP relevance on 2 / 4 / 8 bits;
 * ratios {0, .25, .5, .75, 1}; PPL on held-out text and the measured wire bytes per token per boundary; for every
   allocated plan, the paired window-bootstrap 95 % interval of log PPL(plan) - log PPL(uniform) at each ratio
