@@ -432,27 +432,37 @@ __device__ __forceinline__ uint64_t grp_load(const uint8_t* __restrict__ src, in
   }
   return w;
 }
+// The quantizer of a head group, one definition for grp_pack8 and group_quant_err_kernel: the bits of the group's
+// max|v| over the 8 lanes holding it (NaN / Inf if the group holds one: s, and the decode, non-finite), the scale
+// s = am / qmax with its inverse (0 for an all-zero group), and a value's code as a float.  The decoder returns
+// code * s (grp_unpack8).
+__device__ __forceinline__ uint32_t grp_amax_bits(const float (&v)[8]) {
+  uint32_t amb = umax8(v);
+  amb = umax(amb, __shfl_xor(amb, 1, 64));
+  amb = umax(amb, __shfl_xor(amb, 2, 64));
+  amb = umax(amb, __shfl_xor(amb, 4, 64));
+  return amb;
+}
+struct GrpQuant { float s, inv, qf; };
+__device__ __forceinline__ GrpQuant grp_quant(float am, int qmax) {
+  const float s = am / (float)qmax;
+  return {s, am > 0.f ? 1.f / s : 0.f, (float)qmax};
+}
+__device__ __forceinline__ float grp_q(float v, const GrpQuant& k) { return qround(v * k.inv, k.qf, -k.qf); }
+
 __device__ __forceinline__ void grp_pack8(uint8_t* __restrict__ row, const CodecArgs& a, int col,
                                           const float (&v)[8]) {
   const int lane = threadIdx.x & 63;
   const uint8_t* plan = a.msg + a.off_plan;
   const int g = col >> 6, bits = plan[g];
-  const int qmax = (1 << (bits - 1)) - 1;
-  uint32_t amb = umax8(v);
-  amb = umax(amb, __shfl_xor(amb, 1, 64));
-  amb = umax(amb, __shfl_xor(amb, 2, 64));
-  amb = umax(amb, __shfl_xor(amb, 4, 64));
-  const float am = __uint_as_float(amb);      // NaN / Inf if the group holds one: s, and the decode, non-finite
-  const float s = am / (float)qmax;
-  const float inv = am > 0.f ? 1.f / s : 0.f;
-  const float qf = (float)qmax;
+  const GrpQuant k = grp_quant(__uint_as_float(grp_amax_bits(v)), (1 << (bits - 1)) - 1);
   const uint64_t mask = (1ull << bits) - 1;
   uint64_t w = 0;
 #pragma unroll
-  for (int e = 0; e < 8; ++e) w |= ((uint64_t)(int64_t)(int)qround(v[e] * inv, qf, -qf) & mask) << (bits * e);
+  for (int e = 0; e < 8; ++e) w |= ((uint64_t)(int64_t)(int)grp_q(v[e], k) & mask) << (bits * e);
   const int sub = lane & 7;
   grp_store(row + grp_offset(plan, g) + sub * bits, w, bits);
-  if (sub == 0) *(float*)(row + a.grp_code_bytes + 4 * g) = s;
+  if (sub == 0) *(float*)(row + a.grp_code_bytes + 4 * g) = k.s;
 }
 // A group's place in a row as the MESSAGE's plan bytes give it, for the decoders: byte offset of its stream (never
 // negative: unsigned), its width, and `bad`: a width outside GROUP_BITS (a corrupt or version-mismatched message) in
@@ -523,15 +533,19 @@ __device__ __forceinline__ void wht_lanes(V (&v)[8]) {
     }
   }
 }
-__device__ __forceinline__ void grp_pack8_rot(uint8_t* __restrict__ row, const CodecArgs& a, int col,
-                                              const float (&v)[8]) {
-  float y[8];
+// y = H64 v / 8 of a group (the encoder's rotation; the 1/8 is exact)
+__device__ __forceinline__ void grp_rotate8(const float (&v)[8], float (&y)[8]) {
 #pragma unroll
   for (int e = 0; e < 8; ++e) y[e] = v[e];
   wht8(y);
   wht_lanes(y);
 #pragma unroll
   for (int e = 0; e < 8; ++e) y[e] *= 0.125f;
+}
+__device__ __forceinline__ void grp_pack8_rot(uint8_t* __restrict__ row, const CodecArgs& a, int col,
+                                              const float (&v)[8]) {
+  float y[8];
+  grp_rotate8(v, y);
   grp_pack8(row, a, col, y);
 }
 // As grp_unpack8 (NaN from the first bad group on), but a bad group - uniform over the group's 8 lanes - only zeroes
@@ -758,6 +772,113 @@ __global__ __launch_bounds__(256) void unpack_kernel(CodecArgs a) {
   }
 }
 
+// ---------------------------------------------------------------------------------------------
+// Measured quantization error of the head groups (codec/plan.py allocate_group_bits_measured): for every window b,
+// 64-channel group g, basis (0 plain, 1 Hadamard) and width j of GROUP_BITS,
+//   err[b, g, 0, j] = sum_t sum_c dx_tc^2 (x_tc - q_tc s_t)^2,
+//   err[b, g, 1, j] = the same of y = H64 x / 8 and dy = H64 dx / 8,
+// with q, s exactly grp_pack8's at that width (grp_quant / grp_q) and q s what grp_unpack8 returns; dx == nullptr:
+// every weight 1 in both bases.  H64 / 8 is orthonormal and its own inverse, so dy e is the first-order output change
+// of the decoded rgroup_rot row as dx e is of the rgroup row.  One wave per token row as in pack_kernel (a lane holds
+// 8 consecutive channels of each 512-channel chunk, a group is 8 adjacent lanes); the group's max-abs is taken once
+// per basis and shared by the six widths.  q s is rounded to fp32 before the subtraction and the term is
+// (dx dx) (e e), one rounding per operation (fp contract off): every term has the bits of the CPU oracle's
+// (ops/reference.py group_quant_err), only the order of the sums differs.  A workgroup walks QE_ROWS rows of one window
+// (wave w rows w, w + 4, ...), then sums a group's 8 lanes by shuffles and the 4 waves through LDS in a fixed order
+// into part[b, chunk, g, 2, 6]; group_quant_err_sum_kernel adds the chunks in order.  No atomics: a rerun is
+// bit-identical.
+// A group holding a NaN / Inf gets non-finite sums for all twelve entries (s is non-finite, or q s = 0 * Inf); an
+// all-zero group adds 0.
+constexpr int QE_ROWS = 128;
+constexpr int QE_NW = 6;     // widths: GROUP_BITS
+template <int QMAX>
+__device__ __forceinline__ void qerr_acc8(const float (&v)[8], const float (&w2)[8], float am, float& acc) {
+#pragma clang fp contract(off)
+  const GrpQuant k = grp_quant(am, QMAX);
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    const float r = grp_q(v[e], k) * k.s;
+    const float d = v[e] - r;
+    const float t = w2[e] * (d * d);
+    acc += t;
+  }
+}
+__device__ __forceinline__ void qerr_widths8(const float (&v)[8], const float (&w)[8], float (&acc)[QE_NW]) {
+#pragma clang fp contract(off)
+  const float am = __uint_as_float(grp_amax_bits(v));
+  float w2[8];
+#pragma unroll
+  for (int e = 0; e < 8; ++e) w2[e] = w[e] * w[e];
+  qerr_acc8<1>(v, w2, am, acc[0]);
+  qerr_acc8<3>(v, w2, am, acc[1]);
+  qerr_acc8<7>(v, w2, am, acc[2]);
+  qerr_acc8<15>(v, w2, am, acc[3]);
+  qerr_acc8<31>(v, w2, am, acc[4]);
+  qerr_acc8<127>(v, w2, am, acc[5]);
+}
+
+template <int NCH, class T>
+__global__ __launch_bounds__(256) void group_quant_err_kernel(const T* __restrict__ x, const float* __restrict__ dx,
+                                                              float* __restrict__ part, int S, int H,
+                                                              int chunks) {
+  __shared__ float red[4][NCH * 8][2 * QE_NW];
+  const int b = blockIdx.x / chunks, chunk = blockIdx.x % chunks, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int G = H / 64;
+  const int t0 = chunk * QE_ROWS, t1 = min(S, t0 + QE_ROWS);
+  float acc[NCH][2][QE_NW];
+#pragma unroll
+  for (int c = 0; c < NCH; ++c)
+#pragma unroll
+    for (int k = 0; k < 2 * QE_NW; ++k) acc[c][k / QE_NW][k % QE_NW] = 0.f;
+  for (int t = t0 + wave; t < t1; t += 4) {
+    const size_t row = (size_t)b * S + t;
+#pragma unroll
+    for (int c = 0; c < NCH; ++c) {
+      if (c * 512 >= H) continue;            // wave-uniform: whole groups (H % 64 == 0) leave together below too
+      float v[1][8], d[1][8];
+      load_row8<1>(x + row * H + c * 512, H - c * 512, v);
+      if (dx) load_row8<1>(dx + row * H + c * 512, H - c * 512, d);
+      else fill8(d[0], 1.f);
+      if (c * 512 + lane * 8 >= H) continue;
+      qerr_widths8(v[0], d[0], acc[c][0]);
+      float y[8], dy[8];
+      grp_rotate8(v[0], y);
+      if (dx) grp_rotate8(d[0], dy);
+      else fill8(dy, 1.f);
+      qerr_widths8(y, dy, acc[c][1]);
+    }
+  }
+#pragma unroll
+  for (int c = 0; c < NCH; ++c)
+#pragma unroll
+    for (int k = 0; k < 2 * QE_NW; ++k) {
+      float s = acc[c][k / QE_NW][k % QE_NW];
+      s += __shfl_xor(s, 1, 64);
+      s += __shfl_xor(s, 2, 64);
+      s += __shfl_xor(s, 4, 64);
+      if ((lane & 7) == 0) red[wave][c * 8 + (lane >> 3)][k] = s;
+    }
+  __syncthreads();
+  float* out = part + (size_t)blockIdx.x * G * (2 * QE_NW);
+  for (int i = threadIdx.x; i < G * 2 * QE_NW; i += 256) {
+    const int g = i / (2 * QE_NW), k = i % (2 * QE_NW);
+    out[i] = (red[0][g][k] + red[1][g][k]) + (red[2][g][k] + red[3][g][k]);
+  }
+}
+
+// err[b, i] = sum over the chunks, in order, of part[b, chunk, i]   (i over G x 2 x 6)
+__global__ __launch_bounds__(256) void group_quant_err_sum_kernel(const float* __restrict__ part,
+                                                                  float* __restrict__ err, int chunks, int n,
+                                                                  long long total) {
+  const long long j = (long long)blockIdx.x * 256 + threadIdx.x;   // over B x n
+  if (j >= total) return;
+  const long long b = j / n, i = j - b * n;
+  const float* p = part + (size_t)b * chunks * n + i;
+  float s = 0.f;
+  for (int c = 0; c < chunks; ++c) s += p[(size_t)c * n];
+  err[j] = s;
+}
+
 #define DISPATCH_NCH(H, ...)                                          \
   do {                                                                \
     const int _nch = ((H) / 8 + 63) / 64;                             \
@@ -878,4 +999,30 @@ EDGE_API int edge_unpack(void* x, const void* msg, long long om, long long os, l
                          hipStream_t st) {
   return run_codec<false>(x, (void*)msg, om, os, oh, ol, okv, opl, B, S, H, k, hi_fmt, lo_fmt, scale_mode, qmax_hi,
                           qmax_lo, ch_kind, grp_code_bytes, x_f32, st);
+}
+
+// err [B, H/64, 2, 6] fp32; ws: edge_group_quant_err_chunks(S) * B * H/64 * 12 floats; dx fp32 or null (weights 1)
+EDGE_API int edge_group_quant_err_chunks(int S) { return (S + QE_ROWS - 1) / QE_ROWS; }
+
+template <int NCH, class T>
+static void launch_qerr(dim3 grid, hipStream_t st, const void* x, const float* dx, float* ws, int S, int H,
+                        int chunks) {
+  hipLaunchKernelGGL((group_quant_err_kernel<NCH, T>), grid, dim3(256), 0, st, (const T*)x, dx, ws, S, H, chunks);
+}
+
+EDGE_API int edge_group_quant_err(const void* x, const float* dx, float* err, float* ws, int B, int S, int H,
+                                  int x_is_f32, hipStream_t st) {
+  if (H <= 0 || H % 64 || B < 0 || S <= 0) return (int)hipErrorInvalidValue;
+  const int chunks = edge_group_quant_err_chunks(S);
+  if ((long long)B * chunks > 0x7fffffffll) return (int)hipErrorInvalidValue;
+  const dim3 grid((unsigned)(B * chunks));
+  if (B == 0) { DISPATCH_NCH(H, (void)0); return 0; }   // a bad H is an error whatever B
+  if (x_is_f32) DISPATCH_NCH(H, (launch_qerr<NCH, float>(grid, st, x, dx, ws, S, H, chunks)));
+  else DISPATCH_NCH(H, (launch_qerr<NCH, bf16_t>(grid, st, x, dx, ws, S, H, chunks)));
+  const int rc = (int)hipGetLastError();
+  if (rc) return rc;
+  const int n = H / 64 * 2 * QE_NW;
+  const long long total = (long long)B * n;
+  group_quant_err_sum_kernel<<<(unsigned)((total + 255) / 256), 256, 0, st>>>(ws, err, chunks, n, total);
+  return (int)hipGetLastError();
 }

@@ -41,8 +41,10 @@ Head-group codecs carry their group bit plan in the message; a boundary's plan c
 dequantizing (integer butterflies on the codes, bit-identical on CPU and GPU), so a massive channel no longer sets
 its group's step alone: reconstruction MSE on a randn input with one x100 channel per group is 2.2x (4 bits) / 48x
 (8 bits) below ``rgroup``'s and unchanged on plain Gaussians.  At 3 bits it loses there (0.41x): ``rgroup`` zeroes
-the small channels and its error stays bounded by their variance.  Its plans are allocated from the UNROTATED
-sensitivity / relevance tables; a table for rotated groups needs ``max_c |(H x)_c|^2`` in the LRP engine.
+the small channels and its error stays bounded by their variance.  In the default plan mode its plans are allocated
+from the UNROTATED sensitivity / relevance tables; ``group_plan: "measured"`` allocates them (and ``rgroup``'s) exactly
+against the quantization error the relevance pass measures per group and width in the rotated (plain) basis
+(``plan.allocate_group_bits_measured``, ``channel_group_quant_error.json``).
 
 "hi"/"lo" classes: the ``k = int(ratio * S)`` least important tokens of a
 window (ascending importance, ties broken by position) are the lo class.

@@ -22,14 +22,37 @@ def boundary_group_relevance(table, boundary: int, groups: int) -> list:
     return [float(v) for v in t[min(boundary + 1, t.shape[0] - 1)]]
 
 
-def boundary_group_plan(table, boundary: int, groups: int, avg_bits: float = 4.0) -> tuple:
+GROUP_PLAN_MODES = ("auto", "measured")
+
+
+def boundary_group_plan(table, boundary: int, groups: int, avg_bits: float = 4.0, *, mode: str = "auto",
+                        rot: bool = False) -> tuple:
     """The bit plan of the head-group codec at the boundary after layer ``boundary``.
 
-    ``table`` = ``{"relevance": [layers][G], "sensitivity": [layers][G]}`` (``load_group_tables``): the MSE
-    allocation over the groups' quantization sensitivity when it is there (``allocate_group_bits(model="mse")``),
-    else the first-order allocation over the LRP relevance (``model="linear"``, the round-3 allocator); a plain
-    [layers][G] list is a relevance table; None: the uniform plan (every group at ``avg_bits`` when that is a
-    width, else the MSE allocation of equal weights: the nearest widths, as evenly as the budget allows)."""
+    ``mode="auto"``: ``table`` = ``{"relevance": [layers][G], "sensitivity": [layers][G]}`` (``load_group_tables``):
+    the MSE allocation over the groups' quantization sensitivity when it is there
+    (``allocate_group_bits(model="mse")``), else the first-order allocation over the LRP relevance
+    (``model="linear"``, the round-3 allocator); a plain [layers][G] list is a relevance table; None: the uniform plan
+    (every group at ``avg_bits`` when that is a width, else the MSE allocation of equal weights: the nearest widths,
+    as evenly as the budget allows).
+
+    ``mode="measured"``: the exact allocation (``allocate_group_bits_measured``) against the table's measured
+    quantization error ``table["quant_error"]`` [layers][G][2][widths]: the row of the stream entering layer
+    ``boundary + 1`` (the last row after the last layer, as ``boundary_group_relevance``) in the plain basis, or with
+    ``rot`` (the codec's group rows are rotated, ``rgroup_rot``) the Hadamard basis.  No such table is an error."""
+    if mode not in GROUP_PLAN_MODES:
+        raise ValueError(f"group plan mode must be one of {GROUP_PLAN_MODES}, got {mode!r}")
+    if mode == "measured":
+        qe = table.get("quant_error") if isinstance(table, dict) else None
+        if qe is None:
+            raise ValueError("group plan mode 'measured' needs the measured quantization-error table "
+                             "(channel_group_quant_error.json beside the relevance table; the relevance pass "
+                             "writes it)")
+        qe = torch.as_tensor(qe, dtype=torch.float32)
+        if qe.dim() != 4 or qe.shape[1] != groups or qe.shape[2] != 2 or qe.shape[3] != len(GROUP_BITS):
+            raise ValueError(f"measured quantization-error table is {tuple(qe.shape)}, expected "
+                             f"[layers][{groups}][2][{len(GROUP_BITS)}]")
+        return allocate_group_bits_measured(qe[min(boundary + 1, qe.shape[0] - 1), :, int(bool(rot))], avg_bits)
     if table is None:
         return allocate_group_bits([1.0] * groups, avg_bits, model="mse")
     if isinstance(table, dict) and table.get("sensitivity") is not None:
@@ -92,16 +115,66 @@ def allocate_group_bits(weights, avg_bits: float = 4.0, model: str = "mse", widt
     return tuple(bits)
 
 
+def plan_cost(err, plan, widths=GROUP_BITS) -> float:
+    """sum_g err[g][index of plan[g] in widths]: what a plan costs by a measured table."""
+    return float(sum(float(err[g][widths.index(b)]) for g, b in enumerate(plan)))
+
+
+def allocate_group_bits_measured(err, avg_bits: float = 4.0, min_gain: float = 0.0, widths=GROUP_BITS) -> tuple:
+    """The bit plan that minimises a MEASURED error table: ``err`` [G][len(widths)], err[g][j] the error of group g
+    quantized at ``widths[j]`` bits (one boundary and basis of ``ops.group_quant_err`` /
+    ``channel_group_quant_error.json``).  Returns the exact minimiser of sum_g err[g][b_g] subject to
+    sum_g b_g <= round(avg_bits G), by dynamic programming over (group, bits used) - measured errors need not be
+    convex along the width ladder, so the greedy of ``allocate_group_bits`` is not used.  Ties go to the smaller
+    sum of bits, then to the lexicographically smaller plan.  The uniform plan (``boundary_group_plan(None, ...)``)
+    is returned unless cost(best) < (1 - min_gain) cost(uniform): by the table's own measure the result is never worse
+    than uniform.  A non-finite or negative entry is an error naming its group."""
+    widths = tuple(widths)
+    E = [[float(v) for v in row] for row in (err.tolist() if isinstance(err, torch.Tensor) else err)]
+    G = len(E)
+    for g, row in enumerate(E):
+        if len(row) != len(widths):
+            raise ValueError(f"measured error table: group {g} has {len(row)} entries for the widths {widths}")
+        if any(not (v >= 0.0) or v == float("inf") for v in row):
+            raise ValueError(f"measured error table: group {g} has a non-finite or negative entry {row}")
+    uniform = allocate_group_bits([1.0] * G, avg_bits, model="mse", widths=widths)
+    budget = int(round(avg_bits * G))
+    if budget < min(widths) * G:
+        return uniform
+    # best[u] after g groups: (cost, plan) of the cheapest plan of the first g groups using exactly u bits; at equal
+    # cost the lexicographically smaller plan.  Costs are sums in group order, so equal plans compare equal.
+    best = {0: (0.0, ())}
+    for g in range(G):
+        nxt = {}
+        for u, (c, pl) in best.items():
+            for j, b in enumerate(widths):
+                if u + b > budget:
+                    continue
+                cand = (c + E[g][j], pl + (b,))
+                if u + b not in nxt or cand < nxt[u + b]:
+                    nxt[u + b] = cand
+        best = nxt
+    cost, bits_used, plan = min((c, u, pl) for u, (c, pl) in best.items())
+    if not cost < (1.0 - min_gain) * plan_cost(E, uniform, widths):
+        return uniform
+    return plan
+
+
 def load_group_tables(relevance_path: str):
-    """``channel_group_relevance.json`` and, when the relevance pass wrote it beside, the sensitivity table
-    ``channel_group_sensitivity.json`` -> {"relevance": tensor, "sensitivity": tensor or None}."""
+    """``channel_group_relevance.json`` and, when the relevance pass wrote them beside, the sensitivity table
+    ``channel_group_sensitivity.json`` and the measured quantization-error table
+    ``channel_group_quant_error.json`` ([layers][G][2 bases][widths]) -> {"relevance": tensor, "sensitivity": tensor
+    or None, "quant_error": tensor or None}."""
     import json
     import os
     with open(relevance_path) as f:
         rel = torch.tensor(json.load(f), dtype=torch.float32)
-    sp = os.path.join(os.path.dirname(os.path.abspath(relevance_path)), "channel_group_sensitivity.json")
-    sens = None
-    if os.path.exists(sp):
-        with open(sp) as f:
-            sens = torch.tensor(json.load(f), dtype=torch.float32)
-    return {"relevance": rel, "sensitivity": sens}
+    beside = os.path.dirname(os.path.abspath(relevance_path))
+    extra = {}
+    for key, name in (("sensitivity", "channel_group_sensitivity.json"),
+                      ("quant_error", "channel_group_quant_error.json")):
+        extra[key] = None
+        if os.path.exists(os.path.join(beside, name)):
+            with open(os.path.join(beside, name)) as f:
+                extra[key] = torch.tensor(json.load(f), dtype=torch.float32)
+    return {"relevance": rel, **extra}

@@ -89,8 +89,8 @@ CODECS = {c.name: c for c in [
     # rotated head-group rows (FMT_GRPR): rgroup's bytes, but every group is quantized in the basis of the orthonormal
     # 64-point Walsh-Hadamard transform y = H64 x / 8 (QuaRot / SpinQuant), which spreads a massive channel over its
     # group: max|y| falls by up to 8 and with it the step.  Pays from 4 bits up; at 2 - 3 bits plain rgroup's error on
-    # such a group is bounded by the small channels it zeroes and rotation can lose.  The plan allocator is fed the
-    # UNROTATED sensitivity / relevance tables: a table for rotated groups needs max_c |(H x)_c|^2 in the LRP engine.
+    # such a group is bounded by the small channels it zeroes and rotation can lose.  The model-based plan allocator is
+    # fed the UNROTATED sensitivity / relevance tables; the measured one (codec/plan.py) the error in the rotated basis.
     CodecSpec("rgroup_rot", 17, FMT_GRPR, FMT_GRPR, SC_NONE, uses_ratio=False, needs_importance=False),
 ]}
 GROUP = 64                  # channels per group of FMT_GRP / FMT_GRPR rows
@@ -99,6 +99,11 @@ GROUP_BITS = (2, 3, 4, 5, 6, 8)
 
 def needs_plan(spec: CodecSpec) -> bool:
     return spec.hi_fmt in GRP_FORMATS or spec.lo_fmt in GRP_FORMATS
+
+
+def rotated_groups(spec: CodecSpec) -> bool:
+    """The codec's head-group rows are quantized in the Hadamard basis (FMT_GRPR)."""
+    return FMT_GRPR in (spec.hi_fmt, spec.lo_fmt)
 
 
 def with_plan(spec: CodecSpec, plan) -> CodecSpec:
@@ -428,6 +433,17 @@ def hadamard64(x: torch.Tensor) -> torch.Tensor:
     return (_wht64(x.float().reshape(n, H // GROUP, GROUP)) * 0.125).reshape(n, H)
 
 
+def _grp_quant(blk: torch.Tensor, bits: int):
+    """The quantizer of one 64-channel group of fp32 rows [n, 64] at ``bits``: (codes q [n, 64] as floats, scales s
+    [n]) with s = max|x| / qmax (qmax = 2^(bits-1) - 1) and q = clamp(round(x * (1 / s)), -qmax, qmax), 1 / s taken
+    as 0 for an all-zero group (csrc/codec.hip grp_quant / grp_q); the decoder returns q * s."""
+    qmax = (1 << (bits - 1)) - 1
+    am = blk.abs().amax(-1)
+    s = am / float(qmax)
+    inv = torch.where(am > 0, 1.0 / torch.where(am > 0, s, torch.ones_like(s)), torch.zeros_like(s))
+    return torch.round(blk * inv[:, None]).clamp(-qmax, qmax), s
+
+
 def _grp_pack(rows: torch.Tensor, plan, rot: bool = False) -> torch.Tensor:
     """FMT_GRP rows: per 64-channel group g of b_g bits, s = max|x| / qmax_b (qmax = 2^(b-1) - 1), codes
     clamp(round(x * (1 / s)), -qmax, qmax) packed as a b-bit stream (csrc/codec.hip grp_pack8); then the G fp32
@@ -437,12 +453,7 @@ def _grp_pack(rows: torch.Tensor, plan, rot: bool = False) -> torch.Tensor:
         rows = hadamard64(rows)
     parts, scales = [], []
     for g, b in enumerate(plan):
-        blk = rows[:, g * GROUP:(g + 1) * GROUP].float()
-        qmax = (1 << (b - 1)) - 1
-        am = blk.abs().amax(-1)
-        s = am / float(qmax)
-        inv = torch.where(am > 0, 1.0 / torch.where(am > 0, s, torch.ones_like(s)), torch.zeros_like(s))
-        q = torch.round(blk * inv[:, None]).clamp(-qmax, qmax)
+        q, s = _grp_quant(rows[:, g * GROUP:(g + 1) * GROUP].float(), b)
         parts.append(_grp_bits_pack(q, b))
         scales.append(s)
     sc = torch.stack(scales, 1).contiguous().view(torch.uint8).reshape(n, -1)

@@ -44,6 +44,9 @@ class Params:
     selection: str = "ratio"                 # "ratio" (int(ratio*S) least important) | "top_rho" (mass 1 - ratio kept)
     group_relevance: str = ""                # channel_group_relevance.json (head-group codecs rgroup / rgroup_rot / mixed_rgroup_int8)
     group_avg_bits: float = 4.0              # head-group codecs: average bits per channel of a group-quantized row
+    group_plan: str = "auto"                 # head-group codecs: "auto" (plans from the sensitivity / relevance tables'
+                                             # error model) | "measured" (exact allocation against the measured
+                                             # channel_group_quant_error.json of the relevance pass)
     lrp_engine: str = "auto"                 # relevance pass: "auto" (HIP engine on a GPU, autograd on the CPU) |
                                              # "hip" | "autograd" (AttnLRP rules as torch autograd, any device)
     output_dir: str = "."
@@ -93,6 +96,8 @@ class Params:
             raise ValueError("num_stages must be >= 1")
         if self.selection not in ("ratio", "top_rho"):
             raise ValueError(f"selection must be 'ratio' or 'top_rho', got {self.selection!r}")
+        if self.group_plan not in ("auto", "measured"):
+            raise ValueError(f"group_plan must be 'auto' or 'measured', got {self.group_plan!r}")
 
 
 def resolve_device(p: Params) -> str:

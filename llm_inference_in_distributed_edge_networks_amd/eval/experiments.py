@@ -92,7 +92,7 @@ def importance_sweep(p: Params, default_model: str, out_name: str) -> dict:
                                     "(run Experiments/Relevance/main.py or set params['head_weights'])")
     rows = [SweepMethod(m, m, selection=p.selection) for m in methods]
     sc = SweepConfig(rows, p.layers_of_interest, p.ratios, p.codec, hw, group_relevance=_group_relevance(p),
-                     group_avg_bits=p.group_avg_bits)
+                     group_avg_bits=p.group_avg_bits, group_plan=p.group_plan)
     eng = SweepEngine(model, sc)
     state = _state(p, env, out_name)
     pb = progress_bar(len(wins), env.is_main)
@@ -306,7 +306,7 @@ def pipeline_experiment(p: Params, default_model: str) -> dict:
                 log(f"{m} ratio={r}: resumed from checkpoint")
                 continue
             bcfg = BoundaryConfig(p.codec, float(r), m, hw, selection=p.selection, group_relevance=grel,
-                                  group_avg_bits=p.group_avg_bits)
+                                  group_avg_bits=p.group_avg_bits, group_plan=p.group_plan)
             # one runtime for the whole sweep: the transport (RCCL channels / IPC slot rings) is set up once, only
             # the boundary codec changes between (method, ratio)
             if runner is None:

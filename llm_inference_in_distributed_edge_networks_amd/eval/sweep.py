@@ -66,6 +66,7 @@ class SweepConfig:
     ratio_scale: float = 1.0           # Pythia 'initial' uses ratio in 0..10 meaning 0.1*ratio
     group_relevance: object = None     # head-group codecs: channel-group tables (plan source, PipelineConfig)
     group_avg_bits: float = 4.0
+    group_plan: str = "auto"           # "measured": exact allocation against the measured quantization error
 
     def rows(self) -> list:
         out = []
@@ -169,7 +170,8 @@ class SweepEngine:
             return spec
         G = self.m.cfg.hidden_size // C.wire.GROUP
         return C.wire.with_plan(spec, C.plan.boundary_group_plan(self.sc.group_relevance, L, G,
-                                                                 self.sc.group_avg_bits))
+                                                                 self.sc.group_avg_bits, mode=self.sc.group_plan,
+                                                                 rot=C.wire.rotated_groups(spec)))
 
     def _k(self, ratio, S, spec=None):
         return C.wire.num_lo(spec or self.spec, float(ratio) * self.sc.ratio_scale, S)

@@ -918,3 +918,30 @@ def group_absprod(x: torch.Tensor, dx: torch.Tensor, B: int, S: int, out: torch.
         assert sens_out.dtype == torch.float32 and sens_out.stride() == out.stride() and sens_out.shape == out.shape
     call("edge_group_absprod", ptr(x), ptr(dx), ptr(out), ptr(sens_out), B, S, H, out.stride(0), stream())
     return out
+
+
+def group_quant_err(x: torch.Tensor, dx: torch.Tensor | None, B: int, S: int, out: torch.Tensor | None = None):
+    """[B, H/64, 2, 6] fp32: the measured quantization error of every window's 64-channel groups in the plain (0) and
+    the Hadamard (1) basis at every width of ``codec.GROUP_BITS``, weighted by ``dx``² (``dx`` None: unweighted);
+    see ``reference.group_quant_err``.  ``x`` [B*S, H] fp32 or bf16, ``dx`` fp32; into ``out`` if given."""
+    if not _gpu(x):
+        r = ref.group_quant_err(x, dx, B, S)
+        if out is not None:
+            out.copy_(r)
+            return out
+        return r
+    if x.dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError(f"group_quant_err takes fp32 or bf16 activations, got {x.dtype}")
+    _check_f32(dx)
+    if not x.is_contiguous() or x.dim() != 2 or x.shape[0] != B * S or (dx is not None and dx.shape != x.shape):
+        raise ValueError(f"group_quant_err: x {tuple(x.shape)} / dx must be contiguous [B*S, H] with B*S = {B * S}")
+    H = x.shape[1]
+    G = H // 64
+    if out is None:
+        out = torch.empty(B, G, 2, 6, dtype=torch.float32, device=x.device)
+    if out.dtype != torch.float32 or tuple(out.shape) != (B, G, 2, 6) or not out.is_contiguous():
+        raise ValueError(f"group_quant_err: out must be a contiguous fp32 [{B}, {G}, 2, 6]")
+    ws = torch.empty(B * max(1, lib().edge_group_quant_err_chunks(int(S))) * G * 12, dtype=torch.float32,
+                     device=x.device)
+    call("edge_group_quant_err", ptr(x), ptr(dx), ptr(out), ptr(ws), B, S, H, int(x.dtype == torch.float32), stream())
+    return out

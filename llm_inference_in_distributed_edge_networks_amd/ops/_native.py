@@ -94,6 +94,9 @@ _SIGS = {
     "edge_row_rstd_f32": [c_p, c_p, c_i, c_i, c_f, c_i, c_p],
     "edge_lrp_ln_bwd_f32": [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_p],
     "edge_group_absprod": [c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_p],
+    # measured quantization error of the head groups (csrc/codec.hip): the kernel, and the row chunks its workspace has
+    "edge_group_quant_err": [c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_p],
+    "edge_group_quant_err_chunks": [c_i],
     # debug (csrc/debug.hip): LDS + register-file poison before every kernel under EDGE_POISON=2
     "edge_poison_lds": [c_p],
     "edge_poison_lds_bytes": [],
@@ -145,7 +148,7 @@ def ptr(t) -> int | None:
 
 
 _NO_LAUNCH = {"edge_gemm_set_tile", "edge_gemm_set_ring", "edge_gemm_set_store_wait", "edge_gemm_ssq_parts", "edge_poison_lds", "edge_poison_lds_bytes",
-              "edge_gemm_f32_np_ok"}
+              "edge_gemm_f32_np_ok", "edge_group_quant_err_chunks"}
 
 
 def call(name: str, *args) -> None:

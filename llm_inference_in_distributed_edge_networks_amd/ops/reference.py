@@ -493,3 +493,37 @@ def group_sens(x: torch.Tensor, dx: torch.Tensor, B: int, S: int, group: int = 6
     H = x.shape[-1]
     xg, dg = _f(x).view(B, S, H // group, group), _f(dx).view(B, S, H // group, group)
     return (xg.abs().amax(-1).pow(2) * dg.pow(2).sum(-1)).sum(1)
+
+
+def group_quant_err(x: torch.Tensor, dx: torch.Tensor | None, B: int, S: int) -> torch.Tensor:
+    """[B, H / 64, 2, 6] fp32: the measured quantization error of every window's 64-channel groups, the table
+    ``codec.plan.allocate_group_bits_measured`` allocates against.  For width j of ``codec.wire.GROUP_BITS``
+
+        err[b, g, 0, j] = sum_{t in window b} sum_{c in group g} dx_tc^2 (x_tc - q_tc s_t)^2
+        err[b, g, 1, j] = the same of y = H64 x / 8 and dy = H64 dx / 8 (``wire.hadamard64``)
+
+    with (q, s) the head-group quantizer's codes and scale at that width (``wire._grp_quant``, what ``rgroup`` /
+    ``rgroup_rot`` rows store) and q s what their decoder returns.  H64 / 8 is orthonormal and its own inverse, so
+    dy e is the first-order output change of a decoded ``rgroup_rot`` row as dx e is of an ``rgroup`` row; with
+    independent zero-mean errors the variance is sum dy^2 e^2.  ``dx`` None: every weight 1 in both bases (the
+    reconstruction error ||fake_quant(x) - x||^2).  e and the terms (dx dx) (e e) are formed in fp32, one rounding per
+    operation, as csrc/codec.hip group_quant_err_kernel forms them; the sums run in fp64.  A group holding a NaN / Inf
+    has twelve non-finite entries, an all-zero group adds 0."""
+    from ..codec import wire
+    H = x.shape[-1]
+    G = H // wire.GROUP
+    xf = x.float().reshape(B * S, H)                  # fp32 whatever the input: the codec quantizes fp32 rows
+    df = None if dx is None else dx.float().reshape(B * S, H)
+    out = torch.empty(B, G, 2, len(wire.GROUP_BITS), dtype=torch.float64, device=xf.device)
+    for basis in (0, 1):
+        v = wire.hadamard64(xf) if basis else xf
+        w = None if df is None else (wire.hadamard64(df) if basis else df)
+        for g in range(G):
+            blk = v[:, g * wire.GROUP:(g + 1) * wire.GROUP].contiguous()
+            w2 = None if w is None else w[:, g * wire.GROUP:(g + 1) * wire.GROUP] ** 2
+            for j, bits in enumerate(wire.GROUP_BITS):
+                q, s = wire._grp_quant(blk, bits)
+                e = blk - q * s[:, None]
+                t = e * e if w2 is None else w2 * (e * e)
+                out[:, g, basis, j] = t.double().view(B, S, -1).sum((1, 2))
+    return out.float()

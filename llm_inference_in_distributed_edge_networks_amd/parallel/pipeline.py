@@ -48,6 +48,7 @@ class BoundaryConfig:
     # width
     group_relevance: object = None
     group_avg_bits: float = 4.0
+    group_plan: str = "auto"      # "measured": exact allocation against the tables' measured quantization error
 
     @property
     def spec(self) -> C.CodecSpec:
@@ -61,7 +62,8 @@ class BoundaryConfig:
             return spec
         G = hidden // C.wire.GROUP
         return C.wire.with_plan(spec, C.plan.boundary_group_plan(self.group_relevance, boundary, G,
-                                                                 self.group_avg_bits))
+                                                                 self.group_avg_bits, mode=self.group_plan,
+                                                                 rot=C.wire.rotated_groups(spec)))
 
     @property
     def kvar(self) -> bool:

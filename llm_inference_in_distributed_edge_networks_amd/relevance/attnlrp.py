@@ -186,14 +186,16 @@ def head_relevance(model, ids: torch.Tensor, dtype=torch.float32, via_probs: boo
     return rel, in_rel, mx.detach()
 
 
-def head_relevance_batched(model, ids: torch.Tensor, dtype=torch.float32, group: int = 64, want_sens: bool = False):
+def head_relevance_batched(model, ids: torch.Tensor, dtype=torch.float32, group: int = 64, want_sens: bool = False,
+                           want_qerr: bool = False):
     """``head_relevance`` for B windows at once (windows are independent: each seeds its own max logit), plus the
     relevance of the residual stream entering every layer per ``group``-channel block (head-sized groups):
     chan[b, l, g] = sum over tokens and the group's channels of |x * dx| (LRP Gradient x Input, magnitude: the
     bit-allocation signal of the head-group boundary codec).  Returns (rel [B, layers, heads], in_rel [B],
     seed logit [B], chan [B, layers, H / group][, sens [B, layers, H / group]]: ``want_sens``, the groups'
-    quantization sensitivity, ``ops.reference.group_sens``).  Plain PyTorch ops (autograd, library GEMMs): the
-    reference-precision path of the offline calibration on any device."""
+    quantization sensitivity, ``ops.reference.group_sens``[, qerr [B, layers, H / 64, 2, 6]]: ``want_qerr``, the
+    groups' measured quantization error, ``ops.reference.group_quant_err``).  Plain PyTorch ops (autograd, library
+    GEMMs): the reference-precision path of the offline calibration on any device."""
     B, S = ids.shape
     with torch.enable_grad():
         logits, emb, outs, xs = lrp_forward(model, ids, dtype, keep_probs=False, keep_x=True)
@@ -207,6 +209,12 @@ def head_relevance_batched(model, ids: torch.Tensor, dtype=torch.float32, group:
     if want_sens:
         from ..ops import reference as R
         out += (torch.stack([R.group_sens(x.detach(), x.grad, B, S, group) for x in xs], 1).float(),)
+    if want_qerr:
+        from ..ops import reference as R
+        if group != 64:
+            raise ValueError("the measured quantization error is of 64-channel groups")
+        out += (torch.stack([R.group_quant_err(x.detach().reshape(B * S, H), x.grad.reshape(B * S, H), B, S)
+                             for x in xs], 1),)
     return out
 
 
@@ -263,32 +271,41 @@ def relevance_main(p) -> list:
     acc = torch.zeros(cfg.num_layers, cfg.num_heads, dtype=torch.float64, device=device)
     cacc = torch.zeros(cfg.num_layers, G, dtype=torch.float64, device=device)
     sacc = torch.zeros(cfg.num_layers, G, dtype=torch.float64, device=device)
+    qacc = torch.zeros(cfg.num_layers, G, 2, 6, dtype=torch.float64, device=device)
     pb = progress_bar(len(wins), env.is_main)
     for bi, b in enumerate(batches(ids, wins, max(1, p.window_batch))):
         if bi % env.world_size != env.rank:
             continue
         if eng is not None:
-            rel, _, _, chan, sens = eng.head_relevance(b.ids, want_channels=True, want_sens=True)
+            rel, _, _, chan, sens, qerr = eng.head_relevance(b.ids, want_channels=True, want_sens=True, want_qerr=True)
         else:
-            rel, _, _, chan, sens = head_relevance_batched(model, b.ids.to(device), dtype, want_sens=True)
+            rel, _, _, chan, sens, qerr = head_relevance_batched(model, b.ids.to(device), dtype, want_sens=True,
+                                                                 want_qerr=True)
         acc += rel.double().sum(0)
         cacc += chan.double().sum(0)
         sacc += sens.double().sum(0)
+        qacc += qerr.double().sum(0)
         pb.update(b.B * env.world_size)
     pb.close()
     all_reduce_sum(acc)
     all_reduce_sum(cacc)
     all_reduce_sum(sacc)
+    all_reduce_sum(qacc)
     weights = normalize_per_layer(acc).float().cpu().tolist()
     chan_w = normalize_per_layer(cacc).float().cpu().tolist()
     # the groups' quantization sensitivity, per layer relative to its mean (the allocation only compares the groups
     # of one boundary)
     sens_w = (sacc / sacc.mean(-1, keepdim=True).clamp_min(1e-300)).float().cpu().tolist()
+    # the groups' measured quantization error [layers][G][2 bases][6 widths], per layer relative to its largest finite
+    # entry (only ratios inside one boundary matter to codec.plan.allocate_group_bits_measured)
+    qmax = torch.where(torch.isfinite(qacc), qacc, torch.zeros_like(qacc)).amax((1, 2, 3), keepdim=True)
+    qerr_w = (qacc / qmax.clamp_min(1e-300)).float().cpu().tolist()
     if env.is_main:
         out = os.path.join(p.output_dir, "attention_head_weights.json")
         dump_json(weights, out)
         cout = os.path.join(p.output_dir, "channel_group_relevance.json")
         dump_json(chan_w, cout)
         dump_json(sens_w, os.path.join(p.output_dir, "channel_group_sensitivity.json"))
+        dump_json(qerr_w, os.path.join(p.output_dir, "channel_group_quant_error.json"))
         log(f"wrote {out} and {cout}")
     return weights

@@ -123,9 +123,10 @@ class RelevanceEngine:
 
     @torch.no_grad()
     def head_relevance(self, ids: torch.Tensor, want_channels: bool = False, group: int = 64,
-                       want_sens: bool = False):
+                       want_sens: bool = False, want_qerr: bool = False):
         """ids [B, S] (B windows of equal length) -> (rel [B, layers, heads] fp32, input relevance [B],
-        seed logit [B][, chan [B, layers, H / group]][, sens [B, layers, H / group]]).  rel[b, l, h] = sum_{i,j}
+        seed logit [B][, chan [B, layers, H / group]][, sens [B, layers, H / group]][, qerr [B, layers, H / 64, 2,
+        6]]: ``want_qerr``, the groups' measured quantization error, ``ops.group_quant_err``).  rel[b, l, h] = sum_{i,j}
         A_ij dA_ij of head h, layer l, window b; chan (``want_channels``) = sum over tokens and the group's channels
         of |x * dx| of the residual stream entering layer l (as ``attnlrp.head_relevance_batched``); sens
         (``want_sens``) = the groups' quantization sensitivity (``ops.reference.group_sens``)."""
@@ -145,6 +146,10 @@ class RelevanceEngine:
         chan = torch.zeros(B, cfg.num_layers, H // group, dtype=torch.float32, device=m.device) if want_channels \
             else None
         sens = torch.zeros(B, cfg.num_layers, H // group, dtype=torch.float32, device=m.device) if want_sens else None
+        if want_qerr and group != 64:
+            raise ValueError("the measured quantization error is of 64-channel groups")
+        qerr = torch.zeros(B, cfg.num_layers, H // 64, 2, 6, dtype=torch.float32, device=m.device) if want_qerr \
+            else None
         for i in range(cfg.num_layers - 1, -1, -1):
             L, t, sv = m.layers[i], self.T[i], saves[i]
             rows = sv.get("rows")   # last layer: dx is the seeded rows only [B, H]
@@ -173,6 +178,9 @@ class RelevanceEngine:
                 chan[:, i] = (sv["x"].float() * dx.float()).abs().view(B, S, H // group, group).sum((1, 3))
             if want_sens:
                 sens[:, i] = R.group_sens(sv["x"], dx, B, S, group)
+            if want_qerr:
+                qerr[:, i] = ops.group_quant_err(sv["x"].contiguous(), dx.float().contiguous(), B, S)
             saves[i] = None
         in_rel = (emb.float() * dx.float()).view(B, S, -1).sum((1, 2))
-        return (rel, in_rel, mx) + ((chan,) if want_channels else ()) + ((sens,) if want_sens else ())
+        return (rel, in_rel, mx) + ((chan,) if want_channels else ()) + ((sens,) if want_sens else ()) \
+            + ((qerr,) if want_qerr else ())

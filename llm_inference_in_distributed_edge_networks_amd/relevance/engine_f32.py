@@ -151,9 +151,10 @@ class RelevanceEngineH3:
 
     @torch.no_grad()
     def head_relevance(self, ids: torch.Tensor, want_channels: bool = False, group: int = 64,
-                       want_sens: bool = False):
+                       want_sens: bool = False, want_qerr: bool = False):
         """ids [B, S] -> (rel [B, layers, heads], input relevance [B], seed logit [B][, chan [B, layers, H/64]]
-        [, sens [B, layers, H/64]]), all fp32; the same quantities as ``attnlrp.head_relevance_batched``."""
+        [, sens [B, layers, H/64]][, qerr [B, layers, H/64, 2, 6]]), all fp32; the same quantities as
+        ``attnlrp.head_relevance_batched`` (qerr: the groups' measured quantization error, ``ops.group_quant_err``)."""
         if group != 64:
             raise ValueError("channel groups are 64 channels (one head) wide")
         m, cfg = self.m, self.m.cfg
@@ -171,6 +172,8 @@ class RelevanceEngineH3:
         chan = torch.zeros(B, cfg.num_layers, H // group, dtype=torch.float32, device=m.device) \
             if (want_channels or want_sens) else None
         sens = torch.zeros(B, cfg.num_layers, H // group, dtype=torch.float32, device=m.device) if want_sens else None
+        qerr = torch.zeros(B, cfg.num_layers, H // group, 2, 6, dtype=torch.float32, device=m.device) \
+            if want_qerr else None
         for i in range(cfg.num_layers - 1, -1, -1):
             L, t, sv = m.layers[i], self.T[i], saves[i]
             rows = sv.get("rows")   # last layer: dx is the seeded rows only [B, H]
@@ -210,6 +213,9 @@ class RelevanceEngineH3:
                 dx = ops.lrp_ln_bwd_f32(dh1, sv["rs1"], L["ln1_w"], dh2, L["ln2_w"], dy)
             if want_channels or want_sens:
                 ops.group_absprod(sv["x"], dx, B, S, out=chan[:, i], sens_out=None if sens is None else sens[:, i])
+            if want_qerr:
+                qerr[:, i] = ops.group_quant_err(sv["x"], dx, B, S)
             saves[i] = None
         in_rel = (emb * dx).view(B, -1).sum(1)
-        return (rel, in_rel, mx) + ((chan,) if want_channels else ()) + ((sens,) if want_sens else ())
+        return (rel, in_rel, mx) + ((chan,) if want_channels else ()) + ((sens,) if want_sens else ()) \
+            + ((qerr,) if want_qerr else ())

@@ -12,13 +12,16 @@ message the RCCL transport carries) on the byte-level Qwen2 trained by ``tools/t
 * codecs: the config's codec, the reference Q1 (``ref_int4_global``) at every boundary, and for config 5 the
   head-group codec with allocated plans against the same codec with uniform plans (same bits): "sens" = the MSE
   allocation over the groups' quantization sensitivity on the widths 2-8 (``codec.plan.allocate_group_bits``), "rel"
-  = round 3's first-order allocation over the LRP relevance on 2 / 4 / 8 bits;
+  = round 3's first-order allocation over the LRP relevance on 2 / 4 / 8 bits, "meas" = the exact allocation against
+  the groups' measured quantization error (``codec.plan.allocate_group_bits_measured``; the rotated codec's rows take
+  the table's Hadamard-basis slice);
 * ratios {0, .25, .5, .75, 1}; PPL on held-out text and the measured wire bytes per token per boundary; for every
   allocated plan, the paired window-bootstrap 95 % interval of log PPL(plan) - log PPL(uniform) at each ratio
   (``eval.stats``).
 
-The LRP tables (head weights for ``weighted_importance``, channel-group relevance and sensitivity for the head-group
-plans) are calibrated first on training text with the fp32 relevance engine.  Output: JSON + markdown tables.
+The LRP tables (head weights for ``weighted_importance``, channel-group relevance, sensitivity and measured
+quantization error for the head-group plans) are calibrated first on training text with the fp32 relevance engine.
+Output: JSON + markdown tables.
 """
 import argparse
 import json
@@ -38,8 +41,9 @@ from llm_inference_in_distributed_edge_networks_amd.parallel import (BoundaryCon
 from llm_inference_in_distributed_edge_networks_amd.relevance.attnlrp import (head_relevance_batched,  # noqa: E402
                                                                               normalize_per_layer)
 
-# (pp, method, codec, plan) rows; plan: "rel" = relevance-allocated head-group widths, "uniform" = the same average
-# width in every group, "-" = not a head-group codec
+# (pp, method, codec, plan) rows; plan: "rel" = relevance-allocated head-group widths, "sens" = sensitivity-allocated,
+# "meas" = allocated against the measured quantization error, "uniform" = the same average width in every group,
+# "-" = not a head-group codec
 GRID = [
     # config 3: 2-stage, column-mean importance, mixed int4/int8 per token
     (2, "regular_importance", "mixed_int4_int8", "-"), (2, "regular_importance", "ref_int4_global", "-"),
@@ -50,16 +54,21 @@ GRID = [
     # config 5: 8-stage, LRP-weighted importance, allocated head-group quantization ("@bits" = average width of the
     # group-quantized rows)
     (8, "weighted_importance", "mixed_rgroup_int8", "sens"), (8, "weighted_importance", "mixed_rgroup_int8", "rel"),
+    (8, "weighted_importance", "mixed_rgroup_int8", "meas"),
     (8, "weighted_importance", "mixed_rgroup_int8", "uniform"),
     (8, "weighted_importance", "mixed_rgroup_int8@3", "sens"), (8, "weighted_importance", "mixed_rgroup_int8@3", "rel"),
+    (8, "weighted_importance", "mixed_rgroup_int8@3", "meas"),
     (8, "weighted_importance", "mixed_rgroup_int8@3", "uniform"),
     (8, "weighted_importance", "mixed_int4_int8", "-"), (8, "weighted_importance", "ref_int4_global", "-"),
     (8, "last_row", "mixed_rgroup_int8@3", "rel"), (8, "last_row", "mixed_rgroup_int8@3", "uniform"),
     (8, "weighted_importance", "rgroup@3", "rel"), (8, "weighted_importance", "rgroup@3", "uniform"),
     # the head groups rotated by the 64-point Hadamard transform against the plain ones at the same bytes (rotation
-    # is expected to pay from 4 bits up and may lose at 3); the plans come from the unrotated tables
+    # is expected to pay from 4 bits up and may lose at 3); the "sens" plans come from the unrotated tables, the
+    # "meas" plans of the rotated codec from the error measured in the rotated basis
     (8, "weighted_importance", "rgroup_rot@3", "uniform"), (8, "weighted_importance", "rgroup@4", "uniform"),
     (8, "weighted_importance", "rgroup_rot@4", "uniform"), (8, "weighted_importance", "rgroup_rot@4", "sens"),
+    (8, "weighted_importance", "rgroup@3", "meas"), (8, "weighted_importance", "rgroup_rot@3", "meas"),
+    (8, "weighted_importance", "rgroup@4", "meas"), (8, "weighted_importance", "rgroup_rot@4", "meas"),
 ]
 
 
@@ -103,21 +112,25 @@ def main():
     acc = torch.zeros(cfg.num_layers, cfg.num_heads, dtype=torch.float64, device=dev)
     cacc = torch.zeros(cfg.num_layers, cfg.hidden_size // 64, dtype=torch.float64, device=dev)
     sacc = torch.zeros_like(cacc)
+    qacc = torch.zeros(cfg.num_layers, cfg.hidden_size // 64, 2, 6, dtype=torch.float64, device=dev)
     if dev == "cuda":
         from llm_inference_in_distributed_edge_networks_amd.relevance.engine_f32 import RelevanceEngineH3
         eng = RelevanceEngineH3(m)
-        run = lambda ids: eng.head_relevance(ids, want_channels=True, want_sens=True)   # noqa: E731
+        run = lambda ids: eng.head_relevance(ids, want_channels=True, want_sens=True, want_qerr=True)   # noqa: E731
     else:
-        run = lambda ids: head_relevance_batched(m, ids, want_sens=True)                 # noqa: E731
+        run = lambda ids: head_relevance_batched(m, ids, want_sens=True, want_qerr=True)                 # noqa: E731
     for b in batches(tr, wins, 16, bos=a.bos if a.bos >= 0 else None):
-        rel, _, _, chan, sens = run(b.ids.to(dev))
+        rel, _, _, chan, sens, qerr = run(b.ids.to(dev))
+        qacc += qerr.double().sum(0)
         acc += rel.double().sum(0)
         cacc += chan.double().sum(0)
         sacc += sens.double().sum(0)
     hw = normalize_per_layer(acc).float().cpu()
     grel = normalize_per_layer(cacc).float().cpu()
     gsens = (sacc / sacc.mean(-1, keepdim=True).clamp_min(1e-300)).float().cpu()
-    tables = {"sens": {"relevance": grel, "sensitivity": gsens}, "rel": grel, "uniform": None, "-": None}
+    gqerr = (qacc / qacc.amax((1, 2, 3), keepdim=True).clamp_min(1e-300)).float().cpu()
+    tables = {"sens": {"relevance": grel, "sensitivity": gsens}, "rel": grel, "uniform": None, "-": None,
+              "meas": {"relevance": grel, "sensitivity": gsens, "quant_error": gqerr}}
     print(f"relevance (fp32 engine): {len(wins)} windows in {time.time() - t0:.1f}s", flush=True)
 
     ev = local_text_bytes("eval")
@@ -126,7 +139,8 @@ def main():
     out = {"model": cfg.name, "weights": a.weights, "dtype": "fp32", "device": dev,
            "data": f"python-stdlib-bytes/eval, {len(wins)} windows (max_length 512, stride 32)",
            "ratios": ratios, "group_avg_bits": a.group_bits, "head_weights": hw.tolist(),
-           "channel_group_relevance": grel.tolist(), "channel_group_sensitivity": gsens.tolist(), "rows": []}
+           "channel_group_relevance": grel.tolist(), "channel_group_sensitivity": gsens.tolist(),
+           "channel_group_quant_error": gqerr.tolist(), "rows": []}
     win_nll = {}   # row index -> per ratio: per-window NLL [N] (for the paired intervals)
     weights = None
     for pp, meth, codec_spec, plan in GRID:
@@ -139,7 +153,8 @@ def main():
         pipe = None
         per_ratio = []
         for r in ratios:
-            bc = BoundaryConfig(codec, r, meth, hw, group_relevance=tables[plan], group_avg_bits=gbits)
+            bc = BoundaryConfig(codec, r, meth, hw, group_relevance=tables[plan], group_avg_bits=gbits,
+                                group_plan="measured" if plan == "meas" else "auto")
             if pipe is None:
                 pipe = LocalPipeline(m, pplan, bc)
             else:
@@ -173,7 +188,7 @@ def main():
     # allocated plan vs the uniform plan of the same codec / bits / method / depth, paired over windows
     comps = []
     for ia, ra in enumerate(out["rows"]):
-        if ra["plan"] not in ("sens", "rel"):
+        if ra["plan"] not in ("sens", "rel", "meas"):
             continue
         for ib, rb in enumerate(out["rows"]):
             if (rb["plan"] == "uniform" and rb["codec"] == ra["codec"] and rb["method"] == ra["method"]
