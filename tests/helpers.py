@@ -91,3 +91,129 @@ def kvar_activations(B, S, H, seed, dtype=torch.float32):
     x[S + 5] *= 40
     x[(B * S) // 2 + 1] = 0
     return x.to(dtype)
+
+
+# ---- attention / importance kernels on ragged windows and hard softmax rows (test_attention_edges*.py) -------------
+# one off the 16-row wave tile, the 64-key tile and the 128-row workgroup, and the shortest windows
+EDGE_S = [1, 2, 15, 16, 17, 63, 64, 65, 127, 128, 129, 255, 257]
+# (B, Hq, Hkv): B * Hkv = 6, 9, 17 (window, kv head) groups - below 8 (idle XCDs), just above 8 (one XCD owns two
+# groups: grp = xcd + 8 * (rem / G)) and above 16 (three)
+EDGE_LAYOUTS = [(3, 4, 2), (9, 2, 1), (17, 1, 1)]
+EDGE_LAYOUT_G16 = (1, 16, 1)          # G = 16: the full MFMA tile of attn_lastrow_h3
+# (id, kind, amp): the structure sits in channel 3, the other channels stay random
+EDGE_KINDS = [("rand", "rand", 0.0), ("flat", "flat", 0.0), ("sink30", "sink", 30.0), ("sink150", "sink", 150.0),
+              ("diag60", "diag", 60.0), ("ramp7.5", "ramp", 7.5), ("ramp8", "ramp", 8.0), ("ramp8.5", "ramp", 8.5),
+              ("ramp16", "ramp", 16.0), ("down40", "down", 40.0)]
+EDGE_KIND = {i: (kind, amp) for i, kind, amp in EDGE_KINDS}
+EDGE_KIND_IDS = [i for i, _, _ in EDGE_KINDS]
+LN2 = 0.6931471805599453
+
+
+# A dropped last key shows only where some head's last row puts visible mass on its own key, which a random row of
+# 128 or more keys may not: these (layout, S) take the first seed of the sequence base + 100000 t on which the
+# ``rand`` case meets test_attention_edges.py::test_detection with a margin of two (searched once, asserted there).
+EDGE_SEED_STEP = {((3, 4, 2), 64): 1, ((17, 1, 1), 64): 2, ((9, 2, 1), 127): 2, ((1, 16, 1), 127): 1,
+                  ((3, 4, 2), 128): 1, ((9, 2, 1), 128): 2, ((1, 16, 1), 128): 2, ((3, 4, 2), 129): 4,
+                  ((9, 2, 1), 129): 5, ((1, 16, 1), 129): 4, ((3, 4, 2), 255): 6, ((9, 2, 1), 255): 4,
+                  ((17, 1, 1), 255): 1, ((1, 16, 1), 255): 1, ((3, 4, 2), 257): 4, ((17, 1, 1), 257): 9}
+
+
+def edge_seed(B, Hq, Hkv, S):
+    return 7000 + 1000 * B + 100 * Hq + S + 100000 * EDGE_SEED_STEP.get(((B, Hq, Hkv), S), 0)
+
+
+def attention_case(kind, B, Hq, Hkv, S, amp, seed):
+    """fp32 (q [B, Hq, S, 64] pre-scaled, k, v [B, Hkv, S, 64]) from test_attention_f32's distribution (q = randn / 2,
+    k = 2 randn, v = randn), with one structure on top:
+
+    rand  unchanged: tails and masks.
+    flat  q = 0: a uniform softmax, o_i = mean(v_0 .. v_i), lse_i = log(i + 1), no cancellation to hide behind.
+    sink  q[..., 3] = 1, k[..., 3] = 0, k[:, :, 0, 3] = amp nats: key 0 dominates every row; at amp = 150
+          (> 126 ln 2) every later key underflows.
+    diag  k_j = amp q_j / |q_j|^2 of the group's first q head: q_j . k_j = amp, every new tile raises the row
+          maximum and the rescale factor alpha goes to 0.
+    ramp  q[..., 3] = 1, k[..., j, 3] = (j // 64) amp ln 2: the maximum rises by amp (log2 units) per key tile -
+          just under, at, just over and at twice the lazy-rescale threshold 8.
+    down  ramp with the sign flipped: the maximum sits in tile 0, the tail underflows."""
+    g = torch.Generator().manual_seed(seed)
+    q = torch.randn(B, Hq, S, 64, generator=g) * 0.5
+    k = torch.randn(B, Hkv, S, 64, generator=g) * 2
+    v = torch.randn(B, Hkv, S, 64, generator=g)
+    if kind == "rand":
+        pass
+    elif kind == "flat":
+        q.zero_()
+    elif kind == "sink":
+        q[..., 3] = 1.0
+        k[..., 3] = 0.0
+        k[:, :, 0, 3] = amp
+    elif kind == "diag":
+        q0 = q[:, ::Hq // Hkv]
+        k = amp * q0 / q0.pow(2).sum(-1, keepdim=True)
+    elif kind in ("ramp", "down"):
+        q[..., 3] = 1.0
+        step = (torch.arange(S) // 64).float() * float(amp * LN2)
+        k[..., 3] = step if kind == "ramp" else -step
+    else:
+        raise ValueError(kind)
+    return q.contiguous(), k.contiguous(), v.contiguous()
+
+
+def edge_case(kid, B, Hq, Hkv, S):
+    kind, amp = EDGE_KIND[kid]
+    return attention_case(kind, B, Hq, Hkv, S, amp, edge_seed(B, Hq, Hkv, S))
+
+
+def vt_of(v, S):
+    """V [B, Hkv, S, 64] -> V^T [B, Hkv, 64, s_pad] with zero key padding (the attention kernels' layout)."""
+    from llm_inference_in_distributed_edge_networks_amd.ops import reference as R
+    vt = torch.zeros(*v.shape[:2], 64, R.s_pad(S), dtype=v.dtype)
+    vt[..., :S] = v.transpose(-1, -2)
+    return vt
+
+
+def attention_all64(q, k, v, S, shift=0, pad_last=False):
+    """fp64 (o [B*S, Hq*64], lse, last row, column sums [B, Hq, S]) from one explicit probability matrix, with the
+    mask as a parameter: query i sees keys j <= i + shift (row 0 always keeps key 0); ``pad_last`` hides key S - 1
+    from every row as if it were padding.  shift = 0, pad_last = False is the causal attention; the other settings
+    are the wrong answers an off-by-one tail or mask would give (the detection check of test_attention_edges.py)."""
+    B, Hq = q.shape[:2]
+    G = Hq // k.shape[1]
+    kk, vv = k.double().repeat_interleave(G, 1), v.double().repeat_interleave(G, 1)
+    sc = q.double() @ kk.transpose(-1, -2)
+    i, j = torch.arange(S).view(-1, 1), torch.arange(S).view(1, -1)
+    seen = j <= (i + shift).clamp(0, S - 1)
+    if pad_last and S > 1:
+        seen = seen & (j < S - 1)
+    sc = sc.masked_fill(~seen, float("-inf"))
+    lse = torch.logsumexp(sc, -1)
+    p = torch.exp(sc - lse[..., None])
+    o = (p @ vv).permute(0, 2, 1, 3).reshape(B * S, Hq * 64)
+    return o, lse, p[:, :, S - 1], p.sum(-2)
+
+
+def score_eps(q, k, S):
+    """eps_s = 2^-21 A, A = max over the unmasked (i, j) of sum_d |q_id k_jd|: the score error of 22-bit operand
+    planes (two fp16 planes at a power-of-two scale, or three bf16 planes, keep at least 22 bits of every element)."""
+    G = q.shape[1] // k.shape[1]
+    a = q.double().abs() @ k.double().abs().repeat_interleave(G, 1).transpose(-1, -2)
+    return float(torch.tril(a).max()) * 2.0 ** -21
+
+
+def edge_caps(q, k, v, o_ref, S):
+    """The derived caps of the fp32 kernels' errors against fp64 (and of the CPU fp32 oracle's, the yardstick): a
+    score is off by at most eps_s, a probability then by about 2 eps_s relative; the floors are those of
+    test_attention_f32 / test_importance_stats_f32 at the old shapes.  o, lastrow, colsum: max |err| / max |ref|;
+    lse: max |err|."""
+    e = score_eps(q, k, S)
+    return {"o": 1e-5 + 4 * e * float(v.abs().max()) / max(float(o_ref.abs().max()), 1e-30),
+            "lse": 5e-5 + 2 * e, "lastrow": 2e-6 + 4 * e, "colsum": 5e-6 + 4 * e}
+
+
+def edge_err(name, got, ref):
+    """The error measure of ``edge_caps``; a non-finite output is an infinite error."""
+    got, ref = got.detach().double().cpu().reshape(ref.shape), ref.double()
+    if not torch.isfinite(got).all():
+        return float("inf")
+    d = float((got - ref).abs().max())
+    return d if name == "lse" else d / max(float(ref.abs().max()), 1e-30)

@@ -295,7 +295,8 @@ def test_qkv_rope_h3(B, S, Hq, Hkv, rot, tile, two_term):
 
 
 @pytest.mark.parametrize("B,S,Hq,Hkv,rot", [(2, 512, 14, 2, 64), (2, 100, 14, 2, 64), (1, 2048, 8, 8, 16),
-                                             (3, 200, 14, 2, 0), (64, 512, 14, 2, 64)])
+                                             (3, 200, 14, 2, 0), (64, 512, 14, 2, 64), (3, 1, 14, 2, 64),
+                                             (3, 65, 14, 2, 64), (2, 129, 14, 2, 16)])
 @pytest.mark.parametrize("tile", ["auto", "192", "256"])
 def test_qkv_kv_planes(B, S, Hq, Hkv, rot, tile):
     """K / V^T h3 planes from the fp32 QKV epilogues (128x128, 256x192 and 256x256 tiles) are the split of the fp32
@@ -328,7 +329,8 @@ def test_qkv_kv_planes(B, S, Hq, Hkv, rot, tile):
     assert torch.equal(v, vt2[..., :S].transpose(-1, -2))   # V row-major (AttnLRP), the same values as V^T
 
 
-@pytest.mark.parametrize("B,S,rot", [(2, 512, 64), (3, 98, 64), (64, 512, 64), (3, 200, 0)])
+@pytest.mark.parametrize("B,S,rot", [(2, 512, 64), (3, 98, 64), (64, 512, 64), (3, 200, 0), (3, 65, 64),
+                                     (2, 129, 0)])
 def test_qkv_planes_only(B, S, rot):
     """The planes-only QKV of the model's layers (need_k=False: q + K / V^T planes, no fp32 K / V^T / V rows) on the
     256x192 tiles: q and the planes equal the need_k=True call's bit for bit (partial row tiles, S % 4 != 0, no
@@ -356,7 +358,7 @@ def test_qkv_planes_only(B, S, rot):
 
 
 @pytest.mark.parametrize("B,S,Hq,Hkv", [(2, 512, 14, 2), (3, 100, 14, 2), (1, 2048, 8, 8), (2, 64, 4, 1),
-                                         (2, 200, 14, 2)])
+                                         (2, 200, 14, 2), (3, 1, 14, 2), (3, 65, 14, 2), (3, 129, 4, 1)])
 @pytest.mark.parametrize("h3", [False, True])
 def test_attention_kv_planes_bit_identical(B, S, Hq, Hkv, h3):
     """The LDS-DMA plane-staged attention (K / V^T planes from the QKV epilogue) equals the kernel that splits the
@@ -382,7 +384,7 @@ def test_attention_kv_planes_bit_identical(B, S, Hq, Hkv, h3):
         of, _ = ops.attention(*args, need_lse=True, in_scales=sc, kv_planes=planes)
         assert torch.equal(o4, o1) and torch.equal(l4, l1) and torch.equal(o32, of)
         assert torch.equal(ops.split_h3(o32, s), o1)   # the planes are the split of those rows
-    n_rows = torch.tensor([float(min(31 + 40 * i, S - 2)) for i in range(B)], device=DEV)
+    n_rows = torch.tensor([float(max(0, min(31 + 40 * i, S - 2))) for i in range(B)], device=DEV)
     o3, _ = ops.attention(*args, n_rows=n_rows, h3=s, in_scales=sc, kv_planes=planes)
     W = o1.shape[1]
     for bi in range(B):

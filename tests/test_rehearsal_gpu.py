@@ -37,7 +37,8 @@ def _run(n, extra=(), env_extra=None, self_launch=False, full=False):
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={n}", "--master-addr",
                "127.0.0.1", "--master-port", str(_port())] + ARGS + ["--gpus", str(n)] + list(extra)
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=240)
-    assert r.returncode == 0, r.stderr[-3000:]
+    # the launcher's per-rank summary alone fills 3000 characters: keep enough to show the first rank's own message
+    assert r.returncode == 0, r.stderr[-12000:]
     return json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
 
 
