@@ -115,7 +115,10 @@ LN2 = 0.6931471805599453
 EDGE_SEED_STEP = {((3, 4, 2), 64): 1, ((17, 1, 1), 64): 2, ((9, 2, 1), 127): 2, ((1, 16, 1), 127): 1,
                   ((3, 4, 2), 128): 1, ((9, 2, 1), 128): 2, ((1, 16, 1), 128): 2, ((3, 4, 2), 129): 4,
                   ((9, 2, 1), 129): 5, ((1, 16, 1), 129): 4, ((3, 4, 2), 255): 6, ((9, 2, 1), 255): 4,
-                  ((17, 1, 1), 255): 1, ((1, 16, 1), 255): 1, ((3, 4, 2), 257): 4, ((17, 1, 1), 257): 9}
+                  ((17, 1, 1), 255): 1, ((1, 16, 1), 255): 1, ((3, 4, 2), 257): 4, ((17, 1, 1), 257): 9,
+                  # S = 31 is a length of the AttnLRP cases only (LRP_EDGE_S): the first seed on which the ``rand``
+                  # case meets test_lrp_edges.py::test_detection with a margin of two
+                  ((9, 2, 1), 31): 1}
 
 
 def edge_seed(B, Hq, Hkv, S):
@@ -217,3 +220,156 @@ def edge_err(name, got, ref):
         return float("inf")
     d = float((got - ref).abs().max())
     return d if name == "lse" else d / max(float(ref.abs().max()), 1e-30)
+
+
+# ---- AttnLRP attention backward on ragged windows and hard rows (test_lrp_edges*.py) -------------------------------
+# EDGE_S and one off the 32-row tile both backward sweeps stage (the bf16 dK/dV sweep starts at (kb * 64) & ~31)
+LRP_EDGE_S = sorted(set(EDGE_S) | {31, 32, 33})
+# ... and Qwen2's layout: G = 7 q heads per kv head, so with an odd tile count the group-sum sweep (one workgroup
+# walks the G heads through the same two buffers) crosses a head boundary on either buffer parity
+LRP_LAYOUTS = EDGE_LAYOUTS + [EDGE_LAYOUT_G16, (2, 14, 2)]
+LRP_DO_KINDS = ["rand", "last", "zero_head"]
+LRP_OUTPUTS = ("D", "rel", "dq", "dk", "dv")
+# The row magnitudes are floored at this fraction of the output's largest row magnitude.  Under sink150 / down40 the
+# column mass of most keys is ~e^-150: those rows of dk and dv are 0 in any fp32 arithmetic (exp underflows at
+# e^-103) and ~1e-65 in fp64, a relative error of 1 that says nothing.  The fraction is what the number formats of
+# the fp32 sweeps resolve (csrc/lrp_f32.hip; the bf16 sweeps keep fp32's exponent range on P and dS):
+#   D, dv  P is held on two fp16 planes at the scale 2^14, an absolute step of 2^-39 next to the largest P = 1: a
+#          row 2^-20 below the largest still has 19 bits, finer than every cap.
+#   dq, dk go through dS, split at the fixed scale sd = so sv 2^-21 that rests on the bound |dS| <= 64 max|dO| max|v|.
+#          With so max|dO| > 2^14 and sv max|v| > 2^14 the planes' absolute step is 2^-25 / sd < 2^-32 max|dO| max|v|,
+#          while the largest a_dS (row 0: sum_d |dO_0d| |v_0d|, ~41 for the Gaussian dO and v here) is only ~3 max|dO|
+#          max|v|: the bound is loose by 2^4..2^5, and a row summing n such roundings carries about sqrt(n / 12)
+#          2^-33 / 3 of the largest row magnitude, 2^-32 at n = 257.  A floor of 2^-12 keeps that share of a floored
+#          row at 2^-20 (1e-6), below every yardstick; at 2^-20 it alone would take 2^-12 = 2.4e-4, more than the
+#          caps (the first MI355X run, with 2^-20 throughout, showed exactly that: dk up to 2.1e-4 on rows 1e-7 of
+#          the largest, whose hi plane is an fp16 subnormal, and everything else as the yardstick).
+LRP_FLOOR_FRAC = {"D": 2.0 ** -20, "rel": 2.0 ** -20, "dv": 2.0 ** -20, "dq": 2.0 ** -12, "dk": 2.0 ** -12}
+
+
+# The CPU yardsticks' worst error (``lrp_err`` against fp64) per kind, over every length of LRP_EDGE_S, every layout of
+# LRP_LAYOUTS and every dO kind, rounded up to two digits (test_lrp_edges.py ``yard_f32`` - ops.lrp_attn_bwd on CPU
+# fp32 tensors after the CPU fp32 forward - and ``yard_bf16``, the bf16 sweeps' rounding points emulated on the CPU).
+# flat: the scores are exact (q = 0) and dk is identically 0; sink150: key 0 has probability exactly 1.0 in fp32 and
+# bf16 alike, what is left is the fp32 summation.
+LRP_YARD_WORST = {
+    "f32": {
+        "rand": {"D": 3.6e-06, "rel": 2.0e-06, "dq": 7.7e-07, "dk": 5.1e-06, "dv": 1.5e-05},
+        "flat": {"D": 2.9e-07, "rel": 1.9e-07, "dq": 1.1e-07, "dk": 0.0, "dv": 7.7e-07},
+        "sink30": {"D": 3.7e-06, "rel": 1.6e-06, "dq": 3.5e-06, "dk": 4.8e-06, "dv": 2.8e-05},
+        "sink150": {"D": 9.5e-08, "rel": 6.9e-08, "dq": 1.6e-07, "dk": 7.3e-08, "dv": 3.0e-07},
+        "diag60": {"D": 3.3e-06, "rel": 9.1e-07, "dq": 9.7e-07, "dk": 2.8e-06, "dv": 1.5e-05},
+        "ramp7.5": {"D": 6.1e-06, "rel": 2.4e-06, "dq": 7.1e-07, "dk": 5.8e-06, "dv": 2.6e-05},
+        "ramp8": {"D": 6.0e-06, "rel": 4.0e-06, "dq": 7.3e-07, "dk": 5.9e-06, "dv": 2.6e-05},
+        "ramp8.5": {"D": 5.3e-06, "rel": 3.3e-06, "dq": 6.8e-07, "dk": 5.8e-06, "dv": 2.8e-05},
+        "ramp16": {"D": 7.7e-06, "rel": 2.4e-06, "dq": 1.3e-06, "dk": 9.2e-06, "dv": 3.8e-05},
+        "down40": {"D": 3.0e-06, "rel": 1.1e-06, "dq": 7.2e-07, "dk": 2.4e-06, "dv": 1.5e-05},
+    },
+    "bf16": {
+        "rand": {"D": 1.4e-03, "rel": 1.1e-03, "dq": 8.6e-04, "dk": 1.8e-03, "dv": 3.9e-03},
+        "flat": {"D": 1.4e-03, "rel": 1.1e-03, "dq": 9.0e-04, "dk": 0.0, "dv": 3.9e-03},
+        "sink30": {"D": 1.6e-03, "rel": 9.9e-04, "dq": 1.2e-03, "dk": 1.7e-03, "dv": 3.9e-03},
+        "sink150": {"D": 7.9e-08, "rel": 4.5e-08, "dq": 6.1e-08, "dk": 4.7e-08, "dv": 1.7e-08},
+        "diag60": {"D": 1.5e-03, "rel": 1.2e-03, "dq": 7.3e-04, "dk": 1.4e-03, "dv": 3.9e-03},
+        "ramp7.5": {"D": 1.5e-03, "rel": 1.1e-03, "dq": 8.8e-04, "dk": 1.7e-03, "dv": 3.9e-03},
+        "ramp8": {"D": 1.6e-03, "rel": 1.1e-03, "dq": 8.8e-04, "dk": 1.6e-03, "dv": 3.9e-03},
+        "ramp8.5": {"D": 1.6e-03, "rel": 1.1e-03, "dq": 8.8e-04, "dk": 1.6e-03, "dv": 3.9e-03},
+        "ramp16": {"D": 1.5e-03, "rel": 1.3e-03, "dq": 8.8e-04, "dk": 1.7e-03, "dv": 3.9e-03},
+        "down40": {"D": 1.5e-03, "rel": 9.4e-04, "dq": 8.8e-04, "dk": 1.6e-03, "dv": 3.9e-03},
+    },
+}
+
+
+def lrp_caps(yard, kid, q, k, S):
+    """The caps of the sweeps' errors (``lrp_err``) against fp64: four times the worst error of the CPU yardstick of
+    that precision over every case of the kind (``LRP_YARD_WORST``; the factor test_f32_gpu.py grants over the CPU fp32
+    GEMM), plus, for the fp32 sweeps, 4 eps_s: their scores come from 22-bit planes, so a probability is off by about
+    2 eps_s relative (``edge_caps``), twice that with the LSE of a forward on the same planes, and every output is
+    linear in P.  The bf16 sweeps' scores are exact products of the rounded inputs; their caps never exceed the 2e-2
+    test_lrp_gpu.py grants."""
+    if yard == "bf16":
+        return {n: min(4 * LRP_YARD_WORST[yard][kid][n], 2e-2) for n in LRP_OUTPUTS}
+    e = score_eps(q, k, S)
+    return {n: 4 * LRP_YARD_WORST[yard][kid][n] + 4 * e for n in LRP_OUTPUTS}
+
+
+def lrp_dO(dkind, B, Hq, Hkv, S):
+    """The upstream gradient dO [B * S, Hq * 64] (fp32):
+
+    rand       Gaussian.
+    last       Gaussian on row S - 1 of every window, exactly 0 elsewhere: the gradient of the engine's seed.
+    zero_head  rand with q head 1 zeroed in every window and every q head of kv group 0 zeroed in window 0 (a head /
+               a whole group whose max |dO| is 0: the ``mx == 0`` branch of the power-of-two dO scale)."""
+    g = torch.Generator().manual_seed(edge_seed(B, Hq, Hkv, S) + 50000)
+    dO = torch.randn(B, S, Hq, 64, generator=g)
+    if dkind == "last":
+        dO[:, :S - 1] = 0.0
+    elif dkind == "zero_head":
+        if Hq > 1:
+            dO[:, :, 1] = 0.0
+        dO[0, :, :Hq // Hkv] = 0.0
+    elif dkind != "rand":
+        raise ValueError(dkind)
+    return dO.reshape(B * S, Hq * 64).contiguous()
+
+
+def lrp_all64(q, k, v, dO, S, shift=0, pad_last=False):
+    """fp64 AttnLRP attention backward from one explicit probability matrix, with the mask as a parameter (as
+    ``attention_all64``: o and LSE are computed under the same mask).  Returns (ref, mag):
+
+    ref  D [B, Hq, S], rel [B, Hq], dq, dk, dv [B, Hq, S, 64] by the formulas of ``ops.reference.lrp_attn_bwd``,
+         dk_sum, dv_sum [B, Hkv, S, 64] (the GQA group sums), o [B * S, Hq * 64] and lse [B, Hq, S].
+    mag  per output and row the cancellation-free magnitude - the same expression with every factor replaced by
+         its absolute value, aD = 1/2 sum |o| |dO|, a_dS = P (1/2 |dO| |v|^T + aD), 1/2 a_dS |k|, 1/2 a_dS^T |q|,
+         1/2 P^T |dO| - as the maximum over the row's 64 channels; rel: sum_i aD.  At S = 1, dq and dk are exactly
+         0 in exact arithmetic (dS_00 = P (dA - D) = 0), so an error relative to |ref| would mean nothing."""
+    B, Hq = q.shape[:2]
+    Hkv = k.shape[1]
+    G = Hq // Hkv
+    qd, kk, vv = q.double(), k.double().repeat_interleave(G, 1), v.double().repeat_interleave(G, 1)
+    sc = qd @ kk.transpose(-1, -2)
+    i, j = torch.arange(S).view(-1, 1), torch.arange(S).view(1, -1)
+    seen = j <= (i + shift).clamp(0, S - 1)
+    if pad_last and S > 1:
+        seen = seen & (j < S - 1)
+    sc = sc.masked_fill(~seen, float("-inf"))
+    lse = torch.logsumexp(sc, -1)
+    p = torch.exp(sc - lse[..., None])
+    o = p @ vv
+    dOh = dO.double().view(B, S, Hq, 64).permute(0, 2, 1, 3)
+    D = 0.5 * (o * dOh).sum(-1)
+    dS = p * (0.5 * dOh @ vv.transpose(-1, -2) - D[..., None])
+    ref = {"D": D, "rel": D.sum(-1), "dq": 0.5 * dS @ kk, "dk": 0.5 * dS.transpose(-1, -2) @ qd,
+           "dv": 0.5 * p.transpose(-1, -2) @ dOh}
+    aD = 0.5 * (o.abs() * dOh.abs()).sum(-1)
+    a_dS = p * (0.5 * dOh.abs() @ vv.abs().transpose(-1, -2) + aD[..., None])
+    el = {"dq": 0.5 * a_dS @ kk.abs(), "dk": 0.5 * a_dS.transpose(-1, -2) @ qd.abs(),
+          "dv": 0.5 * p.transpose(-1, -2) @ dOh.abs()}
+    mag = {"D": aD, "rel": aD.sum(-1)}
+    for n in ("dq", "dk", "dv"):
+        mag[n] = el[n].amax(-1)
+    for n in ("dk", "dv"):
+        ref[n + "_sum"] = ref[n].view(B, Hkv, G, S, 64).sum(2)
+        mag[n + "_sum"] = el[n].view(B, Hkv, G, S, 64).sum(2).amax(-1)
+    ref["o"], ref["lse"] = o.permute(0, 2, 1, 3).reshape(B * S, Hq * 64), lse
+    return ref, mag
+
+
+def lrp_err(name, got, ref, mag):
+    """max over rows (window, head, token) of max_d |got - ref| / the row's magnitude, the magnitude floored at
+    ``LRP_FLOOR_FRAC`` (by output; dk_sum / dv_sum as dk / dv) of the output's largest.  A row of magnitude 0 (dk
+    under q = 0, every output of a head whose dO is 0) must be exactly 0, and the output finite: otherwise the error
+    is infinite."""
+    got, ref = got.detach().double().cpu().reshape(ref.shape), ref.double()
+    if not torch.isfinite(got).all():
+        return float("inf")
+    diff = (got - ref).abs()
+    if diff.dim() > mag.dim():
+        diff = diff.amax(-1)
+    zero = mag == 0
+    if bool((diff[zero] != 0).any()):
+        return float("inf")
+    if bool(zero.all()):
+        return 0.0
+    frac = LRP_FLOOR_FRAC[name.replace("_sum", "")]
+    return float((diff / mag.clamp_min(frac * float(mag.max())))[~zero].max())
