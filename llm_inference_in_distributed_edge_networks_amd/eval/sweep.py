@@ -30,7 +30,6 @@ Progress is checkpointed every ``checkpoint_every`` windows and resumed.
 from __future__ import annotations
 
 import json
-import os
 import time
 from dataclasses import dataclass
 
@@ -94,8 +93,7 @@ class SweepEngine:
         self.forward_tokens = 0
         self.wire_bytes = torch.zeros(shape, dtype=torch.float64)
         self.tokens_done = 0
-        # the model's last layer only at the scored rows (see DecoderLM.layer_rows)
-        self.rows_only = os.environ.get("EDGE_LAST_LAYER_ALL_ROWS", "0") in ("", "0")
+        self.rows_only = DecoderLM.scored_rows_default()   # the model's last layer only at the scored rows
         self._dev = None               # [total_nll, sum_window_nll] increments on the model's device
         # the unquantized prefix forward has a fixed launch sequence per batch signature: one HIP graph replay
         need = self._needed()
@@ -150,8 +148,7 @@ class SweepEngine:
                 if k:
                     kinds.add(k)
             if i == last and not kinds and i not in self.layers and self.rows_only:
-                x = m.layer_rows(i, x, B, S, batch.rows, batch.n_rows)    # only the scored rows reach the head
-                rows = torch.arange(x.shape[0], device=x.device)
+                x, rows = m.last_layer_scored(x, B, S, batch.rows, batch.n_rows)
                 continue
             x, st = m.layer(i, x, B, S, stats=tuple(sorted(kinds)) or None)
             for tr in trackers.values():
@@ -226,8 +223,7 @@ class SweepEngine:
                 rows = batch.rows.repeat(V) + off
                 for i in range(L + 1, m.cfg.num_layers):
                     if i == m.cfg.num_layers - 1 and self.rows_only:
-                        x = m.layer_rows(i, x, V * B, S, rows, batch.n_rows.repeat(V))
-                        rows = torch.arange(x.shape[0], device=x.device)
+                        x, rows = m.last_layer_scored(x, V * B, S, rows, batch.n_rows.repeat(V))
                     else:
                         x, _ = m.layer(i, x, V * B, S)
                 # layer-token work in units of full-model forward tokens

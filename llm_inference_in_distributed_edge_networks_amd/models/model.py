@@ -350,12 +350,44 @@ class DecoderLM:
 
         ``stats``: None, "lastrow" (P[S-1, :] per head), "colsum" (column sums of P per head) or a tuple of both.
         """
-        cfg, L = self.cfg, self.layers[i]
-        if L is None:
+        if self.layers[i] is None:
             raise RuntimeError(f"layer {i} is not resident on this stage")
+        kinds = self._stat_kinds(stats)
         if self.h3:
-            return self._layer_h3(i, x, B, S, stats)
+            M = x.shape[0]
+            rstd1 = torch.empty(M, dtype=torch.float32, device=x.device) if self._np_fused(M) else None
+            q, k, o3, lse, h23 = self._attn_h3(i, x, B, S, need_lse="colsum" in kinds, need_k=bool(kinds),
+                                               rstd_out=rstd1)
+            # the scores on the forward's scaled fp16 planes (consistent with its LSE)
+            sc = self.h3_layer[i]
+            st = self._attn_stats(kinds, q, k, lse, S, in_scales=(sc["att_q"], sc["att_k"]))
+            return self._mlp_h3(i, o3, x, h23, rstd1), st
+        q, k, o, lse, h2 = self._attn(i, x, B, S, need_lse="colsum" in kinds)
+        st = self._attn_stats(kinds, q, k, lse, S)
+        return self._mlp(i, o, x, h2, want_ssq=True), st   # the fused-norm path attaches the next layer's ssq
+
+    @staticmethod
+    def _stat_kinds(stats):
+        kinds = () if stats is None else ((stats,) if isinstance(stats, str) else tuple(stats))
+        for kd in kinds:
+            if kd not in ("lastrow", "colsum"):
+                raise ValueError(kd)
+        return kinds
+
+    @staticmethod
+    def _attn_stats(kinds, q, k, lse, S, in_scales=None):
+        """The statistics ``kinds`` of one layer's attention (``in_scales``: the fp32 mode's (s_q, s_k) planes)."""
+        if not kinds:
+            return None
+        return AttnStats(lastrow=ops.attn_lastrow(q, k, S, in_scales=in_scales) if "lastrow" in kinds else None,
+                         colsum=ops.attn_colsum(q, k, lse, S, in_scales=in_scales) if "colsum" in kinds else None)
+
+    def _attn(self, i, x, B, S, need_lse=False, n_rows=None):
+        """bf16 / CPU: norm(s) -> QKV GEMM (+bias+RoPE, +the fused RMSNorm's row scale) -> attention.  Returns
+        (q, k, o, lse, h2); h2 is GPT-NeoX's second LayerNorm of ``x`` (the MLP's input), else None."""
+        cfg, L = self.cfg, self.layers[i]
         Hq, Hkv, D = cfg.num_heads, cfg.num_kv_heads, cfg.head_dim
+        h2 = None
         if self.fuse_norm:
             ssq = getattr(x, "_edge_ssq", None)
             if ssq is None:           # stage input / decoded boundary / embedding: one light kernel
@@ -369,37 +401,24 @@ class DecoderLM:
                 h, h2 = ops.layernorm_dual(x, L["ln1_w"], L["ln1_b"], L["ln2_w"], L["ln2_b"], cfg.norm_eps)
             q, k, vt = ops.qkv_rope(h, L["wqkv"], L["bqkv"], self.cos, self.sin, B, S, Hq, Hkv, D,
                                     cfg.rotary_dim, self.q_scale)
-        kinds = () if stats is None else ((stats,) if isinstance(stats, str) else tuple(stats))
-        for kd in kinds:
-            if kd not in ("lastrow", "colsum"):
-                raise ValueError(kd)
-        o, lse = ops.attention(q, k, vt, S, need_lse=("colsum" in kinds))
-        st = None
-        if kinds:
-            st = AttnStats(lastrow=ops.attn_lastrow(q, k, S) if "lastrow" in kinds else None,
-                           colsum=ops.attn_colsum(q, k, lse, S) if "colsum" in kinds else None)
+        o, lse = ops.attention(q, k, vt, S, need_lse=need_lse, n_rows=n_rows)
+        return q, k, o, lse, h2
+
+    def _mlp(self, i, o, x, h2, want_ssq=False):
+        """bf16 / CPU: O-projection (+residual ``x``) -> MLP (+residual), the down GEMM in place.  ``want_ssq``: the
+        fused-norm path's down GEMM attaches the output's ``_edge_ssq`` (the next layer's RMSNorm-1)."""
+        cfg, L = self.cfg, self.layers[i]
         if self.fuse_norm:
             y = ops.linear(o, L["wo"], residual=x, want_ssq=True)
             a = ops.linear(y, L["wgu_n"], act="swiglu_il", norm=(y._edge_ssq, cfg.norm_eps))
-            y = ops.linear(a, L["wd"], residual=y, out=y, want_ssq=True)   # in place; fresh ssq attached
-        elif cfg.arch == "qwen2":
+            return ops.linear(a, L["wd"], residual=y, out=y, want_ssq=want_ssq)
+        if cfg.arch == "qwen2":
             y = ops.linear(o, L["wo"], residual=x)
-            h = ops.rmsnorm(y, L["ln2_w"], cfg.norm_eps)
-            a = ops.linear(h, L["wgu"], act="swiglu_il")
-            y = ops.linear(a, L["wd"], residual=y, out=y)
-        else:
-            y = ops.linear(o, L["wo"], L["bo"], residual=x)
-            f = ops.linear(h2, L["wfc"], L["bfc"], act="gelu")
-            y = ops.linear(f, L["wproj"], L["bproj"], residual=y, out=y)
-        return y, st
-
-    @staticmethod
-    def _stat_kinds(stats):
-        kinds = () if stats is None else ((stats,) if isinstance(stats, str) else tuple(stats))
-        for kd in kinds:
-            if kd not in ("lastrow", "colsum"):
-                raise ValueError(kd)
-        return kinds
+            a = ops.linear(ops.rmsnorm(y, L["ln2_w"], cfg.norm_eps), L["wgu"], act="swiglu_il")
+            return ops.linear(a, L["wd"], residual=y, out=y)
+        y = ops.linear(o, L["wo"], L["bo"], residual=x)
+        f = ops.linear(h2, L["wfc"], L["bfc"], act="gelu")
+        return ops.linear(f, L["wproj"], L["bproj"], residual=y, out=y)
 
     def _np_fused(self, M: int) -> bool:
         """RMSNorm-2 fused into the O-projection for an M-row layer (linear_h3_np on the GPU's 256x224 tiles)."""
@@ -452,18 +471,6 @@ class DecoderLM:
         f3 = ops.linear_h3(h23, L["wfc3"], sc["a_wfc"], L["bfc"], act="gelu", out_scale=sc["down"])
         return ops.linear_h3(f3, L["wproj3"], sc["a_wproj"], L["bproj"], residual=y, out=y)
 
-    def _layer_h3(self, i, x, B, S, stats):
-        kinds = self._stat_kinds(stats)
-        rstd1 = torch.empty(x.shape[0], dtype=torch.float32, device=x.device) if self._np_fused(x.shape[0]) else None
-        q, k, o3, lse, h23 = self._attn_h3(i, x, B, S, need_lse="colsum" in kinds, need_k=bool(kinds), rstd_out=rstd1)
-        st = None
-        if kinds:   # the scores on the forward's scaled fp16 planes (consistent with its LSE)
-            sc = self.h3_layer[i]
-            qk = (sc["att_q"], sc["att_k"])
-            st = AttnStats(lastrow=ops.attn_lastrow(q, k, S, in_scales=qk) if "lastrow" in kinds else None,
-                           colsum=ops.attn_colsum(q, k, lse, S, in_scales=qk) if "colsum" in kinds else None)
-        return self._mlp_h3(i, o3, x, h23, rstd1), st
-
     def layer_rows(self, i: int, x: torch.Tensor, B: int, S: int, rows: torch.Tensor,
                    n_rows: torch.Tensor | None = None) -> torch.Tensor:
         """Decoder layer ``i`` evaluated only at the flat row indices ``rows`` -> hidden [len(rows), H].
@@ -472,42 +479,28 @@ class DecoderLM:
         K/V projection - attention queries, O-proj, MLP - is needed at those rows only (1/16 of the rows
         with the reference's 512/32 window/stride).  K and V still come from every row.  ``n_rows`` lets
         the attention kernel skip query blocks below the first scored row of each window."""
-        cfg, L = self.cfg, self.layers[i]
-        if L is None:
+        if self.layers[i] is None:
             raise RuntimeError(f"layer {i} is not resident on this stage")
-        Hq, Hkv, D = cfg.num_heads, cfg.num_kv_heads, cfg.head_dim
         rows = rows.to(self.device)
         if self.h3:
-            _, _, o3, _, h23 = self._attn_h3(i, x, B, S, n_rows=n_rows, need_k=False)
-            return self._mlp_h3(i, o3.index_select(0, rows), x.index_select(0, rows),
-                                None if h23 is None else h23.index_select(0, rows))
-        h2 = None
-        if self.fuse_norm:
-            ssq = getattr(x, "_edge_ssq", None)
-            if ssq is None:
-                ssq = ops.row_ssq(x)
-            q, k, vt = ops.qkv_rope(x, L["wqkv_n"], L["bqkv"], self.cos, self.sin, B, S, Hq, Hkv, D,
-                                    cfg.rotary_dim, self.q_scale, norm=(ssq, cfg.norm_eps))
+            (_, _, o, _, h2), mlp = self._attn_h3(i, x, B, S, n_rows=n_rows, need_k=False), self._mlp_h3
         else:
-            if cfg.arch == "qwen2":
-                h = ops.rmsnorm(x, L["ln1_w"], cfg.norm_eps)
-            else:
-                h, h2 = ops.layernorm_dual(x, L["ln1_w"], L["ln1_b"], L["ln2_w"], L["ln2_b"], cfg.norm_eps)
-            q, k, vt = ops.qkv_rope(h, L["wqkv"], L["bqkv"], self.cos, self.sin, B, S, Hq, Hkv, D,
-                                    cfg.rotary_dim, self.q_scale)
-        o, _ = ops.attention(q, k, vt, S, n_rows=n_rows)
-        og, xg = o.index_select(0, rows), x.index_select(0, rows)
-        if self.fuse_norm:
-            y = ops.linear(og, L["wo"], residual=xg, want_ssq=True)
-            a = ops.linear(y, L["wgu_n"], act="swiglu_il", norm=(y._edge_ssq, cfg.norm_eps))
-            return ops.linear(a, L["wd"], residual=y, out=y)
-        if cfg.arch == "qwen2":
-            y = ops.linear(og, L["wo"], residual=xg)
-            a = ops.linear(ops.rmsnorm(y, L["ln2_w"], cfg.norm_eps), L["wgu"], act="swiglu_il")
-            return ops.linear(a, L["wd"], residual=y, out=y)
-        y = ops.linear(og, L["wo"], L["bo"], residual=xg)
-        f = ops.linear(h2.index_select(0, rows), L["wfc"], L["bfc"], act="gelu")
-        return ops.linear(f, L["wproj"], L["bproj"], residual=y, out=y)
+            (_, _, o, _, h2), mlp = self._attn(i, x, B, S, n_rows=n_rows), self._mlp
+        return mlp(i, o.index_select(0, rows), x.index_select(0, rows),
+                   None if h2 is None else h2.index_select(0, rows))
+
+    @staticmethod
+    def scored_rows_default() -> bool:
+        """Whether the runners evaluate the model's last layer at the scored rows only (the one reader of
+        ``EDGE_LAST_LAYER_ALL_ROWS``; read when a runner is built)."""
+        return os.environ.get("EDGE_LAST_LAYER_ALL_ROWS", "0") in ("", "0")
+
+    def last_layer_scored(self, x: torch.Tensor, B: int, S: int, rows: torch.Tensor, n_rows: torch.Tensor):
+        """The model's last layer feeds only the LM head: ``layer_rows`` at the scored rows -> (hidden [len(rows), H],
+        the index of those rows in it - what ``row_nll`` takes in place of ``rows``).  When to take this short cut
+        is the caller's: no statistics wanted from the layer and its output not itself a boundary tensor."""
+        x = self.layer_rows(self.cfg.num_layers - 1, x, B, S, rows, n_rows)
+        return x, torch.arange(x.shape[0], device=x.device)
 
     def final_norm(self, x: torch.Tensor, rows: torch.Tensor | None = None) -> torch.Tensor:
         if self.cfg.arch == "qwen2":

@@ -103,8 +103,8 @@ class StageRunner:
         self.last = stage == plan.num_stages - 1
         self.boundary = None if self.last else self.layers[-1]
         self.stats = StageStats()
-        self.scored_rows_only = os.environ.get("EDGE_LAST_LAYER_ALL_ROWS", "0") in ("", "0")
-        self.rows_only = False
+        self.scored_rows_only = DecoderLM.scored_rows_default()
+        self.rows_only = False       # the last run's x holds just the scored rows, indexed by _rows
         # LRP head table resident on the stage's device once (no host->device copy inside a captured graph)
         hw = bcfg.head_weights
         self.head_weights = None if hw is None else torch.as_tensor(hw).to(model.device, torch.float32).contiguous()
@@ -132,8 +132,7 @@ class StageRunner:
         for i in self.layers:
             need = tr.stats_for(i) if tr is not None else None
             if self.last and i == m.cfg.num_layers - 1 and need is None and self.scored_rows_only:
-                # the model's last layer feeds only the LM head: evaluate it at the scored rows only
-                x = m.layer_rows(i, x, B, S, batch.rows, batch.n_rows)
+                x, self._rows = m.last_layer_scored(x, B, S, batch.rows, batch.n_rows)
                 self.rows_only = True
                 continue
             x, st = m.layer(i, x, B, S, stats=need)
@@ -191,10 +190,7 @@ class StageRunner:
 
     def finish(self, x, batch: WindowBatch) -> torch.Tensor:
         """Per-window mean NLL [B] (last stage)."""
-        rows = batch.rows
-        if self.rows_only:           # x already holds just the scored rows, in batch.rows order
-            rows = torch.arange(x.shape[0], device=x.device)
-        nll = self.model.row_nll(x, rows, batch.targets)
+        nll = self.model.row_nll(x, self._rows if self.rows_only else batch.rows, batch.targets)
         return window_nll(nll, batch)
 
 

@@ -27,8 +27,14 @@ from ..ops import reference as R
 from ..models.model import DecoderLM
 
 
+class RelevancePass:
+    """The pass both engines run: forward with saves, seed on the last row of each window, the reverse layer loop and
+    the per-layer tables.  An engine supplies ``_layer_weights`` (the backward GEMMs' weights of one layer),
+    ``_forward``, ``_seed``, ``_backward_layer``, ``_tables`` and ``_input_relevance``."""
+    # ``_tables`` fills chan and sens in one kernel over 64-channel groups: no other group width, and the chan table
+    # exists whenever sens is wanted
+    fused_tables = False
 
-class RelevanceEngine:
     def __init__(self, model: DecoderLM):
         self.m = model
         cfg = model.cfg
@@ -37,24 +43,69 @@ class RelevanceEngine:
         if any(L is None for L in model.layers) or model.w.get("embed") is None or model.w.get("head") is None:
             raise ValueError("relevance engine needs the whole model resident")
         self.qwen = cfg.arch == "qwen2"
-        self.T = []          # per-layer transposed / folded weights of the backward GEMMs
-        for L in model.layers:
-            t = {}
-            if self.qwen:
-                wqkv_n = L.get("wqkv_n")
-                wgu_n = L.get("wgu_n")
-                if wqkv_n is None:
-                    wqkv_n = ops.reference.fold_norm_weight(L["wqkv"], L["ln1_w"]).contiguous()
-                    wgu_n = ops.reference.fold_norm_weight(L["wgu"], L["ln2_w"]).contiguous()
-                t.update(wqkv_n=wqkv_n, wgu_n=wgu_n, wqkvT=wqkv_n.t().contiguous(), woT=L["wo"].t().contiguous(),
-                         wguT=wgu_n.t().contiguous(), wdT=L["wd"].t().contiguous())
-            else:
-                t.update(wqkvT=L["wqkv"].t().contiguous(), woT=L["wo"].t().contiguous(),
-                         wfcT=L["wfc"].t().contiguous(), wprojT=L["wproj"].t().contiguous())
-            self.T.append(t)
+        self.T = [self._layer_weights(L) for L in model.layers]
+
+    @staticmethod
+    def _to_all_rows(rows: torch.Tensor, n: int, *ts):
+        """The last layer's gradients at the seeded rows ``rows`` -> at all ``n`` rows, zero elsewhere."""
+        return [None if t is None else
+                torch.zeros(n, t.shape[1], dtype=t.dtype, device=t.device).index_copy_(0, rows, t) for t in ts]
+
+    @torch.no_grad()
+    def head_relevance(self, ids: torch.Tensor, want_channels: bool = False, group: int = 64,
+                       want_sens: bool = False, want_qerr: bool = False):
+        """ids [B, S] (B windows of equal length) -> (rel [B, layers, heads] fp32, input relevance [B],
+        seed logit [B][, chan [B, layers, H / group]][, sens [B, layers, H / group]][, qerr [B, layers, H / 64, 2,
+        6]]: ``want_qerr``, the groups' measured quantization error, ``ops.group_quant_err``).  rel[b, l, h] = sum_{i,j}
+        A_ij dA_ij of head h, layer l, window b; chan (``want_channels``) = sum over tokens and the group's channels
+        of |x * dx| of the residual stream entering layer l (as ``attnlrp.head_relevance_batched``); sens
+        (``want_sens``) = the groups' quantization sensitivity (``ops.reference.group_sens``)."""
+        if group != 64 and self.fused_tables:
+            raise ValueError("channel groups are 64 channels (one head) wide")
+        if group != 64 and want_qerr:
+            raise ValueError("the measured quantization error is of 64-channel groups")
+        m, cfg = self.m, self.m.cfg
+        ids = ids.to(m.device)
+        B, S = ids.shape
+        H = cfg.hidden_size
+        emb, x, saves = self._forward(ids)
+        dx, mx = self._seed(x, B, S)   # x, dx: the seeded rows only [B, H] (the last layer's ``rows``)
+
+        def table(want, *shape):
+            return torch.zeros(B, cfg.num_layers, *shape, dtype=torch.float32, device=m.device) if want else None
+        rel = table(True, cfg.num_heads)
+        chan = table(want_channels or (want_sens and self.fused_tables), H // group)
+        sens = table(want_sens, H // group)
+        qerr = table(want_qerr, H // 64, 2, 6)
+        for i in range(cfg.num_layers - 1, -1, -1):
+            sv = saves[i]
+            rel[:, i], dx = self._backward_layer(i, dx, sv)
+            self._tables(i, sv["x"], dx, B, S, group, chan, sens, qerr)
+            saves[i] = None
+        in_rel = self._input_relevance(emb, dx, B, S)
+        return (rel, in_rel, mx) + ((chan,) if want_channels else ()) + ((sens,) if want_sens else ()) \
+            + ((qerr,) if want_qerr else ())
+
+
+class RelevanceEngine(RelevancePass):
+    def _layer_weights(self, L: dict) -> dict:
+        """Transposed / norm-folded weights of one layer's backward GEMMs."""
+        if not self.qwen:
+            return dict(wqkvT=L["wqkv"].t().contiguous(), woT=L["wo"].t().contiguous(),
+                        wfcT=L["wfc"].t().contiguous(), wprojT=L["wproj"].t().contiguous())
+        wqkv_n = L.get("wqkv_n")
+        wgu_n = L.get("wgu_n")
+        if wqkv_n is None:
+            wqkv_n = ops.reference.fold_norm_weight(L["wqkv"], L["ln1_w"]).contiguous()
+            wgu_n = ops.reference.fold_norm_weight(L["wgu"], L["ln2_w"]).contiguous()
+        return dict(wqkv_n=wqkv_n, wgu_n=wgu_n, wqkvT=wqkv_n.t().contiguous(), woT=L["wo"].t().contiguous(),
+                    wguT=wgu_n.t().contiguous(), wdT=L["wd"].t().contiguous())
 
     # ------------------------------------------------------------------------------------------------
     def _forward(self, ids: torch.Tensor):
+        # The with-saves sequence, kept apart from ``DecoderLM.layer`` (and from the fp32 engine's) on purpose: it
+        # launches different kernels - ``row_ssq`` + ``row_rscale`` per layer, the raw-emitting SwiGLU GEMM, no
+        # ``want_ssq`` on the down GEMM - and a ``save=`` switch would put those branches into the hot forward.
         m, cfg = self.m, self.m.cfg
         B, S = ids.shape
         H, Hq, Hkv, D = cfg.hidden_size, cfg.num_heads, cfg.num_kv_heads, cfg.head_dim
@@ -121,66 +172,35 @@ class RelevanceEngine:
             g = g - g.mean(-1, keepdim=True)
         return g.to(x.dtype).contiguous(), mx
 
-    @torch.no_grad()
-    def head_relevance(self, ids: torch.Tensor, want_channels: bool = False, group: int = 64,
-                       want_sens: bool = False, want_qerr: bool = False):
-        """ids [B, S] (B windows of equal length) -> (rel [B, layers, heads] fp32, input relevance [B],
-        seed logit [B][, chan [B, layers, H / group]][, sens [B, layers, H / group]][, qerr [B, layers, H / 64, 2,
-        6]]: ``want_qerr``, the groups' measured quantization error, ``ops.group_quant_err``).  rel[b, l, h] = sum_{i,j}
-        A_ij dA_ij of head h, layer l, window b; chan (``want_channels``) = sum over tokens and the group's channels
-        of |x * dx| of the residual stream entering layer l (as ``attnlrp.head_relevance_batched``); sens
-        (``want_sens``) = the groups' quantization sensitivity (``ops.reference.group_sens``)."""
+    def _backward_layer(self, i: int, dx: torch.Tensor, sv: dict):
         m, cfg = self.m, self.m.cfg
-        ids = ids.to(m.device)
-        B, S = ids.shape
-        Hq, Hkv = cfg.num_heads, cfg.num_kv_heads
-        emb, x, saves = self._forward(ids)
-        if saves[-1].get("rows") is None:   # (A/B: the last layer ran on every row) seed its last rows only
-            dx, mx = self._seed(x.view(B, S, -1)[:, -1].contiguous(), B, S)
-            dx = torch.zeros(B * S, x.shape[1], dtype=dx.dtype, device=dx.device).index_copy_(
-                0, torch.arange(B, device=dx.device) * S + (S - 1), dx)
+        L, t = m.layers[i], self.T[i]
+        B, Hq, S, _ = sv["q"].shape
+        dh2 = None
+        if self.qwen:
+            dm = ops.linear(dx, t["wdT"])
+            dy = ops.linear_rowscale(ops.lrp_swiglu_bwd(dm, sv["gu"]), t["wguT"], sv["rs2"], residual=dx)
         else:
-            dx, mx = self._seed(x, B, S)
-        rel = torch.zeros(B, cfg.num_layers, Hq, dtype=torch.float32, device=m.device)
-        H = cfg.hidden_size
-        chan = torch.zeros(B, cfg.num_layers, H // group, dtype=torch.float32, device=m.device) if want_channels \
-            else None
-        sens = torch.zeros(B, cfg.num_layers, H // group, dtype=torch.float32, device=m.device) if want_sens else None
-        if want_qerr and group != 64:
-            raise ValueError("the measured quantization error is of 64-channel groups")
-        qerr = torch.zeros(B, cfg.num_layers, H // 64, 2, 6, dtype=torch.float32, device=m.device) if want_qerr \
-            else None
-        for i in range(cfg.num_layers - 1, -1, -1):
-            L, t, sv = m.layers[i], self.T[i], saves[i]
-            rows = sv.get("rows")   # last layer: dx is the seeded rows only [B, H]
-            if self.qwen:
-                dm = ops.linear(dx, t["wdT"])
-                dy = ops.linear_rowscale(ops.lrp_swiglu_bwd(dm, sv["gu"]), t["wguT"], sv["rs2"], residual=dx)
-            else:
-                dh2 = ops.linear(ops.lrp_gelu_bwd(ops.linear(dx, t["wprojT"]), sv["a"]), t["wfcT"])
-                dy = dx
-            dO = ops.linear(dy, t["woT"])
-            if rows is not None:   # back to every row: zero outside the seeded rows
-                dO = torch.zeros(B * S, dO.shape[1], dtype=dO.dtype, device=dO.device).index_copy_(0, rows, dO)
-                dy = torch.zeros(B * S, H, dtype=dy.dtype, device=dy.device).index_copy_(0, rows, dy)
-                if not self.qwen:
-                    dh2 = torch.zeros(B * S, H, dtype=dh2.dtype, device=dh2.device).index_copy_(0, rows, dh2)
-            _, r, dq, dk, dv = ops.lrp_attn_bwd(sv["q"], sv["k"], sv["v"], sv["o"], dO, sv["lse"])
-            rel[:, i] = r
-            dqkv = ops.lrp_rope_pack(dq, dk, dv, m.cos, m.sin, B, S, Hq, Hkv, cfg.rotary_dim, m.q_scale,
-                                     dtype=dx.dtype)
-            if self.qwen:
-                dx = ops.linear_rowscale(dqkv, t["wqkvT"], sv["rs1"], residual=dy)
-            else:
-                dh1 = ops.linear(dqkv, t["wqkvT"])
-                dx = ops.lrp_ln_bwd(dh1, sv["rs1"], L["ln1_w"], dh2, sv["rs1"], L["ln2_w"], dy)
-            if want_channels:
-                chan[:, i] = (sv["x"].float() * dx.float()).abs().view(B, S, H // group, group).sum((1, 3))
-            if want_sens:
-                sens[:, i] = R.group_sens(sv["x"], dx, B, S, group)
-            if want_qerr:
-                qerr[:, i] = ops.group_quant_err(sv["x"].contiguous(), dx.float().contiguous(), B, S)
-            saves[i] = None
-        in_rel = (emb.float() * dx.float()).view(B, S, -1).sum((1, 2))
-        return (rel, in_rel, mx) + ((chan,) if want_channels else ()) + ((sens,) if want_sens else ()) \
-            + ((qerr,) if want_qerr else ())
+            dh2 = ops.linear(ops.lrp_gelu_bwd(ops.linear(dx, t["wprojT"]), sv["a"]), t["wfcT"])
+            dy = dx
+        dO = ops.linear(dy, t["woT"])
+        if "rows" in sv:   # last layer: dx is the seeded rows only [B, H]
+            dO, dy, dh2 = self._to_all_rows(sv["rows"], B * S, dO, dy, dh2)
+        _, r, dq, dk, dv = ops.lrp_attn_bwd(sv["q"], sv["k"], sv["v"], sv["o"], dO, sv["lse"])
+        dqkv = ops.lrp_rope_pack(dq, dk, dv, m.cos, m.sin, B, S, Hq, cfg.num_kv_heads, cfg.rotary_dim, m.q_scale,
+                                 dtype=dx.dtype)
+        if self.qwen:
+            return r, ops.linear_rowscale(dqkv, t["wqkvT"], sv["rs1"], residual=dy)
+        dh1 = ops.linear(dqkv, t["wqkvT"])
+        return r, ops.lrp_ln_bwd(dh1, sv["rs1"], L["ln1_w"], dh2, sv["rs1"], L["ln2_w"], dy)
+
+    def _tables(self, i, x, dx, B, S, group, chan, sens, qerr):
+        if chan is not None:
+            chan[:, i] = (x.float() * dx.float()).abs().view(B, S, -1, group).sum((1, 3))
+        if sens is not None:
+            sens[:, i] = R.group_sens(x, dx, B, S, group)
+        if qerr is not None:
+            qerr[:, i] = ops.group_quant_err(x.contiguous(), dx.float().contiguous(), B, S)
+
+    def _input_relevance(self, emb, dx, B, S):
+        return (emb.float() * dx.float()).view(B, S, -1).sum((1, 2))

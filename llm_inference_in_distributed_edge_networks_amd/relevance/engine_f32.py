@@ -38,47 +38,44 @@ import torch
 
 from .. import ops
 from ..models.model import DecoderLM
+from .engine import RelevancePass
 
 
+class RelevanceEngineH3(RelevancePass):
+    fused_tables = True   # ``ops.group_absprod``
 
-class RelevanceEngineH3:
     def __init__(self, model: DecoderLM):
-        self.m = model
-        cfg = model.cfg
         if not model.h3:
             raise ValueError("RelevanceEngineH3 needs a model in the fp32 (h3) execution mode")
-        if cfg.head_dim != 64:
-            raise ValueError("relevance engine is specialised for head_dim 64")
-        if any(L is None for L in model.layers) or model.w.get("embed") is None or model.w.get("head") is None:
-            raise ValueError("relevance engine needs the whole model resident")
-        self.qwen = cfg.arch == "qwen2"
-        R = ops.reference
+        super().__init__(model)
 
+    def _layer_weights(self, L: dict) -> dict:
+        """The transposed weights of one layer's backward GEMMs, split once, with their product scales."""
         def t3(w):
-            w3, s = R.h3_weight(w.t().contiguous())
+            w3, s = ops.reference.h3_weight(w.t().contiguous())
             return w3, 1.0 / s
-        self.T = []
-        for L in model.layers:
-            t = {}
-            if self.qwen:
-                # the RMSNorm weights stay out of the transposes (applied on the GEMMs' output columns, colscale):
-                # the transposes of bf16 / fp16-valued weights are then exact in fp16 - two products, not three
-                t["wqkvT3"], t["a_qkvT"] = t3(L["wqkv"])
-                t["wguT3"], t["a_guT"] = t3(L["wgu"])
-                t["wdT3"], t["a_dT"] = t3(L["wd"])
-                t["c_swiglu"] = ops.lrp_swiglu_scale(L["wd"], L["wgu"], L["ln2_w"])
-                # bound of the gate|up input-gradient GEMM's product per unit of its input row scale:
-                # max_c |norm_w[c]| sum_k |W[k, c]| (dy's h3 planes come from that GEMM's epilogue)
-                t["c_gu"] = float((L["wgu"].float().abs().sum(0) * L["ln2_w"].float().abs()).max())
-            else:
-                t["wqkvT3"], t["a_qkvT"] = t3(L["wqkv"])
-                t["wfcT3"], t["a_fcT"] = t3(L["wfc"])
-                t["wprojT3"], t["a_projT"] = t3(L["wproj"])
-            t["woT3"], t["a_oT"] = t3(L["wo"])
-            self.T.append(t)
+        t = {}
+        t["wqkvT3"], t["a_qkvT"] = t3(L["wqkv"])
+        if self.qwen:
+            # the RMSNorm weights stay out of the transposes (applied on the GEMMs' output columns, colscale):
+            # the transposes of bf16 / fp16-valued weights are then exact in fp16 - two products, not three
+            t["wguT3"], t["a_guT"] = t3(L["wgu"])
+            t["wdT3"], t["a_dT"] = t3(L["wd"])
+            t["c_swiglu"] = ops.lrp_swiglu_scale(L["wd"], L["wgu"], L["ln2_w"])
+            # bound of the gate|up input-gradient GEMM's product per unit of its input row scale:
+            # max_c |norm_w[c]| sum_k |W[k, c]| (dy's h3 planes come from that GEMM's epilogue)
+            t["c_gu"] = float((L["wgu"].float().abs().sum(0) * L["ln2_w"].float().abs()).max())
+        else:
+            t["wfcT3"], t["a_fcT"] = t3(L["wfc"])
+            t["wprojT3"], t["a_projT"] = t3(L["wproj"])
+        t["woT3"], t["a_oT"] = t3(L["wo"])
+        return t
 
     # ------------------------------------------------------------------------------------------------
     def _forward(self, ids: torch.Tensor):
+        # The with-saves sequence, kept apart from ``DecoderLM.layer`` (and from the bf16 engine's) on purpose: it
+        # launches different kernels - ``rstd_out`` norms, ``v_rows`` / ``f32_out``, ``linear_h3_swiglu_raw``, an
+        # unfused fc + ``act_h3`` on GPT-NeoX - and a ``save=`` switch would put those branches into the hot forward.
         m, cfg = self.m, self.m.cfg
         B, S = ids.shape
         Hq, Hkv, D, eps = cfg.num_heads, cfg.num_kv_heads, cfg.head_dim, cfg.norm_eps
@@ -149,73 +146,46 @@ class RelevanceEngineH3:
             g = g - g.mean(-1, keepdim=True)
         return g.contiguous(), mx
 
-    @torch.no_grad()
-    def head_relevance(self, ids: torch.Tensor, want_channels: bool = False, group: int = 64,
-                       want_sens: bool = False, want_qerr: bool = False):
-        """ids [B, S] -> (rel [B, layers, heads], input relevance [B], seed logit [B][, chan [B, layers, H/64]]
-        [, sens [B, layers, H/64]][, qerr [B, layers, H/64, 2, 6]]), all fp32; the same quantities as
-        ``attnlrp.head_relevance_batched`` (qerr: the groups' measured quantization error, ``ops.group_quant_err``)."""
-        if group != 64:
-            raise ValueError("channel groups are 64 channels (one head) wide")
+    def _backward_layer(self, i: int, dx: torch.Tensor, sv: dict):
         m, cfg = self.m, self.m.cfg
-        ids = ids.to(m.device)
-        B, S = ids.shape
-        Hq, Hkv, H = cfg.num_heads, cfg.num_kv_heads, cfg.hidden_size
-        emb, x, saves = self._forward(ids)
-        if saves[-1].get("rows") is None:   # (A/B: the last layer ran on every row) seed its last rows only
-            dx, mx = self._seed(x.view(B, S, -1)[:, -1].contiguous(), B, S)
-            dx = torch.zeros(B * S, x.shape[1], dtype=dx.dtype, device=dx.device).index_copy_(
-                0, torch.arange(B, device=dx.device) * S + (S - 1), dx)
+        L, t, sc = m.layers[i], self.T[i], m.h3_layer[i]
+        B, Hq, S, _ = sv["q"].shape
+        dh2 = None
+        dx3, rinv = ops.split_h3_dyn(dx)
+        if self.qwen:
+            # dm GEMM + SwiGLU rule in one kernel (the rule's planes at the weights' a-priori bound)
+            dgu3, rinv_gu = ops.linear_h3_lrp_swiglu(dx3, t["wdT3"], t["a_dT"], sv["gu"], t["c_swiglu"], rinv,
+                                                     post=sv["rs2"])
+            # dy and its h3 planes in one GEMM: |dy| <= |dx| + rinv_gu 2^15 c_gu, |dx| < 2^15 rinv
+            dy, dy3, rinv_y = ops.linear_h3(dgu3, t["wguT3"], t["a_guT"], rscale=rinv_gu, residual=dx,
+                                            colscale=L["ln2_w"], planes_bound=(rinv, rinv_gu, t["c_gu"]))
         else:
-            dx, mx = self._seed(x, B, S)
-        rel = torch.zeros(B, cfg.num_layers, Hq, dtype=torch.float32, device=m.device)
-        chan = torch.zeros(B, cfg.num_layers, H // group, dtype=torch.float32, device=m.device) \
-            if (want_channels or want_sens) else None
-        sens = torch.zeros(B, cfg.num_layers, H // group, dtype=torch.float32, device=m.device) if want_sens else None
-        qerr = torch.zeros(B, cfg.num_layers, H // group, 2, 6, dtype=torch.float32, device=m.device) \
-            if want_qerr else None
-        for i in range(cfg.num_layers - 1, -1, -1):
-            L, t, sv = m.layers[i], self.T[i], saves[i]
-            rows = sv.get("rows")   # last layer: dx is the seeded rows only [B, H]
-            dx3, rinv = ops.split_h3_dyn(dx)
-            if self.qwen:
-                # dm GEMM + SwiGLU rule in one kernel (the rule's planes at the weights' a-priori bound)
-                dgu3, rinv_gu = ops.linear_h3_lrp_swiglu(dx3, t["wdT3"], t["a_dT"], sv["gu"], t["c_swiglu"], rinv,
-                                                         post=sv["rs2"])
-                # dy and its h3 planes in one GEMM: |dy| <= |dx| + rinv_gu 2^15 c_gu, |dx| < 2^15 rinv
-                dy, dy3, rinv_y = ops.linear_h3(dgu3, t["wguT3"], t["a_guT"], rscale=rinv_gu, residual=dx,
-                                                colscale=L["ln2_w"], planes_bound=(rinv, rinv_gu, t["c_gu"]))
-            else:
-                dp = ops.linear_h3(dx3, t["wprojT3"], t["a_projT"], rscale=rinv)
-                dfc3, rinv_fc = ops.lrp_gelu_bwd_h3(dp, sv["a"])
-                dh2 = ops.linear_h3(dfc3, t["wfcT3"], t["a_fcT"], rscale=rinv_fc)
-                dy, dy3, rinv_y = dx, dx3, rinv           # parallel residual: the attention branch sees dx
-            dO = ops.linear_h3(dy3, t["woT3"], t["a_oT"], rscale=rinv_y)
-            if rows is not None:   # back to every row: zero outside the seeded rows
-                dO = torch.zeros(B * S, dO.shape[1], dtype=dO.dtype, device=dO.device).index_copy_(0, rows, dO)
-                dy = torch.zeros(B * S, H, dtype=dy.dtype, device=dy.device).index_copy_(0, rows, dy)
-                if not self.qwen:
-                    dh2 = torch.zeros(B * S, H, dtype=dh2.dtype, device=dh2.device).index_copy_(0, rows, dh2)
-            # dk, dv summed over each GQA group in the kernel where it can (else the per-q-head partials)
-            sc = m.h3_layer[i]   # the forward attention's plane scales: the sweeps run on the same scaled fp16 planes
-            _, r, dq, dk, dv = ops.lrp_attn_bwd(sv["q"], sv["k"], sv["v"], sv["o"], dO, sv["lse"],
-                                                gqa_sum=ops.lrp_gqa_sum_native(sv["q"]),
-                                                in_scales=(sc["att_q"], sc["att_k"], sc["o"]))
-            rel[:, i] = r
-            dqkv3, rinv_q = ops.lrp_rope_pack_h3(dq, dk, dv, m.cos, m.sin, B, S, Hq, Hkv, cfg.rotary_dim, m.q_scale,
-                                                 post=sv["rs1"] if self.qwen else None)
-            if self.qwen:
-                # (dx is re-split from its own row maxima at the next layer: bound-derived scales would compound -
-                # rinv_q, rinv_gu are themselves a-priori bounds - and lose the planes' range within a few layers)
-                dx = ops.linear_h3(dqkv3, t["wqkvT3"], t["a_qkvT"], rscale=rinv_q, residual=dy, colscale=L["ln1_w"])
-            else:
-                dh1 = ops.linear_h3(dqkv3, t["wqkvT3"], t["a_qkvT"], rscale=rinv_q)
-                dx = ops.lrp_ln_bwd_f32(dh1, sv["rs1"], L["ln1_w"], dh2, L["ln2_w"], dy)
-            if want_channels or want_sens:
-                ops.group_absprod(sv["x"], dx, B, S, out=chan[:, i], sens_out=None if sens is None else sens[:, i])
-            if want_qerr:
-                qerr[:, i] = ops.group_quant_err(sv["x"], dx, B, S)
-            saves[i] = None
-        in_rel = (emb * dx).view(B, -1).sum(1)
-        return (rel, in_rel, mx) + ((chan,) if want_channels else ()) + ((sens,) if want_sens else ()) \
-            + ((qerr,) if want_qerr else ())
+            dp = ops.linear_h3(dx3, t["wprojT3"], t["a_projT"], rscale=rinv)
+            dfc3, rinv_fc = ops.lrp_gelu_bwd_h3(dp, sv["a"])
+            dh2 = ops.linear_h3(dfc3, t["wfcT3"], t["a_fcT"], rscale=rinv_fc)
+            dy, dy3, rinv_y = dx, dx3, rinv           # parallel residual: the attention branch sees dx
+        dO = ops.linear_h3(dy3, t["woT3"], t["a_oT"], rscale=rinv_y)
+        if "rows" in sv:   # last layer: dx is the seeded rows only [B, H]
+            dO, dy, dh2 = self._to_all_rows(sv["rows"], B * S, dO, dy, dh2)
+        # dk, dv summed over each GQA group in the kernel where it can (else the per-q-head partials); the sweeps run
+        # on the forward attention's scaled fp16 planes
+        _, r, dq, dk, dv = ops.lrp_attn_bwd(sv["q"], sv["k"], sv["v"], sv["o"], dO, sv["lse"],
+                                            gqa_sum=ops.lrp_gqa_sum_native(sv["q"]),
+                                            in_scales=(sc["att_q"], sc["att_k"], sc["o"]))
+        dqkv3, rinv_q = ops.lrp_rope_pack_h3(dq, dk, dv, m.cos, m.sin, B, S, Hq, cfg.num_kv_heads, cfg.rotary_dim,
+                                             m.q_scale, post=sv["rs1"] if self.qwen else None)
+        if self.qwen:
+            # (dx is re-split from its own row maxima at the next layer: bound-derived scales would compound -
+            # rinv_q, rinv_gu are themselves a-priori bounds - and lose the planes' range within a few layers)
+            return r, ops.linear_h3(dqkv3, t["wqkvT3"], t["a_qkvT"], rscale=rinv_q, residual=dy, colscale=L["ln1_w"])
+        dh1 = ops.linear_h3(dqkv3, t["wqkvT3"], t["a_qkvT"], rscale=rinv_q)
+        return r, ops.lrp_ln_bwd_f32(dh1, sv["rs1"], L["ln1_w"], dh2, L["ln2_w"], dy)
+
+    def _tables(self, i, x, dx, B, S, group, chan, sens, qerr):
+        if chan is not None:
+            ops.group_absprod(x, dx, B, S, out=chan[:, i], sens_out=None if sens is None else sens[:, i])
+        if qerr is not None:
+            qerr[:, i] = ops.group_quant_err(x, dx, B, S)
+
+    def _input_relevance(self, emb, dx, B, S):
+        return (emb * dx).view(B, -1).sum(1)
