@@ -10,7 +10,8 @@
 // A token whose bit is set belongs to the low-precision ("lo") class.  Rows of each class are stored in
 // token order; a row's slot is the popcount of the mask bits before it, so the receiver needs nothing
 // but the mask.  Row formats: 0 bf16, 1 int8, 2 int4 (two's-complement nibbles, even element in the low
-// nibble), 3 int2 (ternary, 4 per byte).  Scale modes: 0 per token (fp32 [B*S]), 1 per window for the
+// nibble), 3 int2 (ternary, 4 per byte), 9 fp16, 10 scaled fp16 (16-bit wires, below).
+// Scale modes: 0 per token (fp32 [B*S]), 1 per window for the
 // lo class (fp32 [B], reference Q1 "one global max-abs" int4), 2 per channel (fp32 [B*H]; reference
 // channel_8/4/1_max store max|x_c|, channel_1_mean stores mean_c + 1e-8), 3 none (pass-through).
 // Activations are bf16 or fp32 (the fp32 execution mode); row format 4 keeps a row in fp32 (the reference leaves
@@ -18,7 +19,24 @@
 #include "common.h"
 
 enum { FMT_BF16 = 0, FMT_INT8 = 1, FMT_INT4 = 2, FMT_INT2 = 3, FMT_F32 = 4, FMT_MXFP4 = 5, FMT_MXFP8 = 6, FMT_GRP = 7,
-       FMT_GRPR = 8 };
+       FMT_GRPR = 8, FMT_F16 = 9, FMT_F16S = 10 };
+// 16-bit wire formats of the rows a codec keeps in the activation dtype (codec/wire.py with_native_wire: the NATIVE
+// class of a codec resolves to one of them instead of the activation dtype, so fp32 activations cross at 2 B per
+// element).  FMT_BF16 (above): round to nearest even.  FMT_F16: IEEE binary16, the fp32 value converted with round to
+// nearest even (the compiler's conversion, never a round-toward-zero pack); subnormals and -0 are kept; a finite value
+// that rounds past 65504 encodes as +-Inf and decodes non-finite - loud; FMT_F16S or FMT_BF16 is the choice for
+// unbounded data.  FMT_F16S (scaled fp16, self-scaled): row = [H binary16 codes][one fp32 p], 2 H + 4 bytes, so rows
+// are only 4-byte aligned and every access to them is 4 bytes wide.  With a the row's max|x| (on bit patterns, NaN
+// propagates): a NaN / Inf -> p = a itself (the codes are don't-care, every channel decodes non-finite); a = 0 ->
+// p = 1; else p = 2^k, k = clamp(E - 141, -112, 113) with E the biased exponent field of a (0 for a denormal;
+// E - 141 = E - 127 - 14).  p and inv = 2^-k are built from integer bit patterns, both normal floats.  Code of channel
+// c: fp16_rne(x_c * inv); decode: float(code_c) * p - one fp32 multiply each, no add after a multiply anywhere, so
+// nothing for fp contraction to fuse.  With k unclamped a * inv is in [2^14, 2^15): no finite row overflows fp16, and
+// |x' - x| <= max(2^-11 |x|, 2^(k - 25)); only a value within half an fp16 ulp of 2^128 (a >= 2^128 - 2^116, the
+// fp32 maximum included) decodes to Inf, as it does in bf16.  Below a = 2^-98 the lower clamp holds k at -112: finite
+// and bounded, not accurate.  Messages with FMT_F16 / FMT_F16S rows run the W16 instantiations of pack_kernel /
+// unpack_kernel (every such branch under `if constexpr (W16)`), so the instantiations every other codec runs keep
+// their instruction stream; no native-hi codec has head-group lo rows, so ROT x W16 is rejected (run_codec).
 // Head-group rows (FMT_GRP): every 64-channel group g (one head's width) has its own bit width b_g in {2, 3, 4, 5, 6, 8}
 // (the plan: one byte per group in the message at off_plan, chosen from the boundary's channel-group sensitivity) and
 // its own max-abs scale s = max|x| / qmax_b (qmax = 2^(b-1) - 1: 1 / 3 / 7 / 15 / 31 / 127): row = [group 0 codes
@@ -54,23 +72,28 @@ struct CodecArgs {
   int grp_code_bytes;           // FMT_GRP / FMT_GRPR: sum over groups of 8 b_g (row = codes + 4 G scale bytes)
 };
 
+template <bool W16>
 __device__ __forceinline__ int fmt_row_bytes(int fmt, int H) {
+  if constexpr (W16) {
+    if (fmt == FMT_F16) return 2 * H;
+    if (fmt == FMT_F16S) return 2 * H + 4;
+  }
   return fmt == FMT_F32 ? 4 * H : fmt == FMT_BF16 ? 2 * H : fmt == FMT_INT8 ? H : fmt == FMT_INT4 ? H / 2 :
          fmt == FMT_MXFP4 ? H / 2 + H / 32 : fmt == FMT_MXFP8 ? H + H / 32 : H / 4;
 }
-template <bool ROT>
+template <bool ROT, bool W16>
 __device__ __forceinline__ int row_bytes(const CodecArgs& a, int fmt) {
   if constexpr (ROT) {
     if (fmt == FMT_GRPR) return a.grp_code_bytes + 4 * (a.H / 64);
   }
-  return fmt == FMT_GRP ? a.grp_code_bytes + 4 * (a.H / 64) : fmt_row_bytes(fmt, a.H);
+  return fmt == FMT_GRP ? a.grp_code_bytes + 4 * (a.H / 64) : fmt_row_bytes<W16>(fmt, a.H);
 }
 // Formats whose rows carry their own scales (or none): no entry in the message's scale section.  A macro, and the
 // rotated format joined with `|`: the compiler simplifies the body of an inlined function on its own first, and the
 // rotated pack instantiations then allocate 66 / 82 instead of 56 / 74 VGPRs (NCH 2 / 4: a wave per SIMD less).
-#define SELF_SCALED(ROT, fmt) \
+#define SELF_SCALED(ROT, W16, fmt) \
   (((fmt) == FMT_BF16 || (fmt) == FMT_F32 || (fmt) == FMT_MXFP4 || (fmt) == FMT_MXFP8 || (fmt) == FMT_GRP) | \
-   ((ROT) && (fmt) == FMT_GRPR))
+   ((ROT) && (fmt) == FMT_GRPR) | ((W16) && ((fmt) == FMT_F16 || (fmt) == FMT_F16S)))
 
 // Max-abs reductions of the codec propagate NaN (a unit holding a NaN / Inf must decode non-finite, and fmaxf drops a
 // NaN operand): they run on the bit pattern of |x| as an unsigned integer.  For non-negative floats the integer order
@@ -222,19 +245,19 @@ __device__ __forceinline__ void kvar_prefix(const CodecArgs& a, int b, int& Kb, 
 // among the class's rows of its window (lo_prefix), the class's rows of the windows before (b k / b (S - k) for fixed
 // k, the k vector's prefix sum for variable k, whose hi section starts right after the Sum k lo rows).
 struct RowSlot { uint8_t* p; int fmt, qmax, b; };
-template <bool ROT>
+template <bool ROT, bool W16>
 __device__ __forceinline__ RowSlot row_slot(const CodecArgs& a, int row) {
   const int b = row / a.S, j = row - b * a.S;
   const uint32_t* mask = (const uint32_t*)(a.msg + a.off_mask) + (size_t)b * a.mw;
   bool is_lo;
   const int slot_lo = lo_prefix(mask, a.mw, j, is_lo);
   const int fmt = is_lo ? a.lo_fmt : a.hi_fmt;
-  const int rb = row_bytes<ROT>(a, fmt);
+  const int rb = row_bytes<ROT, W16>(a, fmt);
   uint8_t* p;
   if (a.off_kvec >= 0) {
     int Kb, Kt;
     kvar_prefix(a, b, Kb, Kt);
-    const long long off_hi = a.off_lo + (((long long)Kt * row_bytes<ROT>(a, a.lo_fmt) + 15) & ~15ll);
+    const long long off_hi = a.off_lo + (((long long)Kt * row_bytes<ROT, W16>(a, a.lo_fmt) + 15) & ~15ll);
     p = is_lo ? a.msg + a.off_lo + ((size_t)Kb + slot_lo) * rb
               : a.msg + off_hi + ((size_t)b * a.S - Kb + (j - slot_lo)) * rb;
   } else {
@@ -574,12 +597,37 @@ __device__ __forceinline__ void grp_unpack8_rot(const uint8_t* __restrict__ row,
   for (int e = 0; e < 8; ++e) o[e] = k.bad ? __builtin_nanf("") : (float)q[e] * sc;
 }
 
-template <int NCH, class T, bool ROT = false>
+// FMT_F16 / FMT_F16S: 8 values <-> 4 words of two binary16 codes (even channel in the low half), each word its own
+// 4-byte access (FMT_F16S rows are only 4-byte aligned); the conversions are the compiler's (round to nearest even,
+// fp16 subnormals kept).
+__device__ __forceinline__ void f16_store8(uint8_t* __restrict__ dst, const float (&v)[8], float inv) {
+#pragma unroll
+  for (int e = 0; e < 4; ++e) ((uint32_t*)dst)[e] = pack_h2(v[2 * e] * inv, v[2 * e + 1] * inv);
+}
+__device__ __forceinline__ void f16_load8(const uint8_t* __restrict__ src, float (&o)[8], float p) {
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const f16x2_t h = __builtin_bit_cast(f16x2_t, ((const uint32_t*)src)[e]);
+    o[2 * e] = (float)h[0] * p;
+    o[2 * e + 1] = (float)h[1] * p;
+  }
+}
+// The scale of an FMT_F16S row from the bits of its max|x| (see the header): p and inv = 1 / p.
+struct F16Scale { float p, inv; };
+__device__ __forceinline__ F16Scale f16s_scale(uint32_t amb) {
+  const int E = (int)(amb >> 23);
+  if (E == 255) return {__uint_as_float(amb), 1.f};   // NaN / Inf: p = a, every channel decodes non-finite
+  if (amb == 0) return {1.f, 1.f};
+  const int k = min(max(E - 141, -112), 113);
+  return {__uint_as_float((uint32_t)(127 + k) << 23), __uint_as_float((uint32_t)(127 - k) << 23)};
+}
+
+template <int NCH, class T, bool ROT = false, bool W16 = false>
 __global__ __launch_bounds__(256) void pack_kernel(CodecArgs a) {
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= a.B * a.S) return;
   const int lane = threadIdx.x & 63;
-  const RowSlot rs = row_slot<ROT>(a, row);
+  const RowSlot rs = row_slot<ROT, W16>(a, row);
   uint8_t* dst = rs.p;
   const int fmt = rs.fmt, qmax = rs.qmax, b = rs.b;
   float v[NCH][8];
@@ -588,7 +636,7 @@ __global__ __launch_bounds__(256) void pack_kernel(CodecArgs a) {
 
   // scale / quantiser for this row
   float inv = 0.f, mul = 0.f;  // code = round(x * inv) for token & channel; window mode uses ref formula
-  const bool raw = SELF_SCALED(ROT, fmt);
+  const bool raw = SELF_SCALED(ROT, W16, fmt);
   if (raw && a.scale_mode == SC_TOKEN && lane == 0) scales[row] = 0.f;
   if (!raw) {
     if (a.scale_mode == SC_TOKEN) {
@@ -607,6 +655,17 @@ __global__ __launch_bounds__(256) void pack_kernel(CodecArgs a) {
   }
   const float qmaxf = (float)qmax;
   const float qminf = a.scale_mode == SC_WINDOW ? -(float)(qmax + 1) : -(float)qmax;
+  float inv16 = 1.f;   // FMT_F16S: 1 / p of the row (FMT_F16: 1, an exact multiply)
+  if constexpr (W16) {
+    if (fmt == FMT_F16S) {
+      uint32_t amb = 0;
+#pragma unroll
+      for (int c = 0; c < NCH; ++c) amb = umax(amb, umax8(v[c]));
+      const F16Scale k = f16s_scale(wave_umax(amb));
+      inv16 = k.inv;
+      if (lane == 0) *(float*)(dst + 2 * a.H) = k.p;
+    }
+  }
 #pragma unroll
   for (int c = 0; c < NCH; ++c) {
     const int col = (c * 64 + lane) * 8;
@@ -637,6 +696,12 @@ __global__ __launch_bounds__(256) void pack_kernel(CodecArgs a) {
       for (int e = 0; e < 4; ++e) w[e] = pack_bf2(v[c][2 * e], v[c][2 * e + 1]);
       *(u32x4_t*)(dst + col * 2) = w;
       continue;
+    }
+    if constexpr (W16) {
+      if (fmt == FMT_F16 || fmt == FMT_F16S) {
+        f16_store8(dst + col * 2, v[c], inv16);
+        continue;
+      }
     }
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
@@ -687,25 +752,37 @@ __device__ __forceinline__ void store8(float* dst, const float (&o)[8]) {
   *(f32x4_t*)(dst + 4) = f32x4_t{o[4], o[5], o[6], o[7]};
 }
 
-template <int NCH, class T, bool ROT = false>
+template <int NCH, class T, bool ROT = false, bool W16 = false>
 __global__ __launch_bounds__(256) void unpack_kernel(CodecArgs a) {
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= a.B * a.S) return;
   const int lane = threadIdx.x & 63;
-  const RowSlot rs = row_slot<ROT>(a, row);
+  const RowSlot rs = row_slot<ROT, W16>(a, row);
   const uint8_t* src = rs.p;
   const int fmt = rs.fmt, qmax = rs.qmax, b = rs.b;
   const float* scales = (const float*)(a.msg + a.off_scale);
   float s = 0.f;
-  if (!SELF_SCALED(ROT, fmt)) {
+  if (!SELF_SCALED(ROT, W16, fmt)) {
     if (a.scale_mode == SC_TOKEN) s = scales[row];
     else if (a.scale_mode == SC_WINDOW) s = scales[b];
   }
   T* out = (T*)a.x + (size_t)row * a.H;
+  float p16 = 1.f;   // FMT_F16S: the row's p (FMT_F16: 1, an exact multiply)
+  if constexpr (W16) {
+    if (fmt == FMT_F16S) p16 = *(const float*)(src + 2 * a.H);
+  }
 #pragma unroll
   for (int c = 0; c < NCH; ++c) {
     const int col = (c * 64 + lane) * 8;
     if (col >= a.H) continue;
+    if constexpr (W16) {
+      if (fmt == FMT_F16 || fmt == FMT_F16S) {
+        float o[8];
+        f16_load8(src + col * 2, o, p16);
+        store8(out + col, o);
+        continue;
+      }
+    }
     if (fmt == FMT_BF16 || fmt == FMT_F32) {
       float o[8];
       if (fmt == FMT_F32) {
@@ -954,19 +1031,23 @@ EDGE_API int edge_rowmax(const float* in, float* out, int R, int H, hipStream_t 
 // A message with FMT_GRPR rows goes to the ROT instantiations (which handle every other format too).
 static bool has_fmt(int hi_fmt, int lo_fmt, int fmt) { return hi_fmt == fmt || lo_fmt == fmt; }
 
-template <bool PACK, int NCH, class T, bool ROT>
+template <bool PACK, int NCH, class T, bool ROT, bool W16 = false>
 static void launch_codec(dim3 grid, hipStream_t st, const CodecArgs& a) {
-  if constexpr (PACK) hipLaunchKernelGGL((pack_kernel<NCH, T, ROT>), grid, dim3(256), 0, st, a);
-  else hipLaunchKernelGGL((unpack_kernel<NCH, T, ROT>), grid, dim3(256), 0, st, a);
+  if constexpr (PACK) hipLaunchKernelGGL((pack_kernel<NCH, T, ROT, W16>), grid, dim3(256), 0, st, a);
+  else hipLaunchKernelGGL((unpack_kernel<NCH, T, ROT, W16>), grid, dim3(256), 0, st, a);
 }
 
-// edge_pack / edge_unpack: argument checks, CodecArgs and the (ROT x activation dtype) x NCH dispatch.
+// edge_pack / edge_unpack: argument checks, CodecArgs and the (ROT | W16 | plain) x activation dtype x NCH dispatch.
+// A message with FMT_F16 / FMT_F16S rows goes to the W16 instantiations (which handle every format but FMT_GRPR);
+// together with FMT_GRPR rows it is rejected before anything is launched.
 template <bool PACK>
 static int run_codec(void* x, void* msg, long long om, long long os, long long oh, long long ol, long long okv,
                      long long opl, int B, int S, int H, int k, int hi_fmt, int lo_fmt, int scale_mode, int qmax_hi,
                      int qmax_lo, int ch_kind, int grp_code_bytes, int x_f32, hipStream_t st) {
   if (H % 32) return (int)hipErrorInvalidValue;
   const bool rot = has_fmt(hi_fmt, lo_fmt, FMT_GRPR);
+  const bool w16 = has_fmt(hi_fmt, lo_fmt, FMT_F16) || has_fmt(hi_fmt, lo_fmt, FMT_F16S);
+  if (rot && w16) return (int)hipErrorInvalidValue;
   if ((rot || has_fmt(hi_fmt, lo_fmt, FMT_GRP)) && (H % 64 || opl < 0 || grp_code_bytes <= 0))
     return (int)hipErrorInvalidValue;
   CodecArgs a;
@@ -981,6 +1062,8 @@ static int run_codec(void* x, void* msg, long long om, long long os, long long o
   const dim3 grid((rows + 3) / 4);
   if (rot && x_f32) DISPATCH_NCH(H, (launch_codec<PACK, NCH, float, true>(grid, st, a)));
   else if (rot) DISPATCH_NCH(H, (launch_codec<PACK, NCH, bf16_t, true>(grid, st, a)));
+  else if (w16 && x_f32) DISPATCH_NCH(H, (launch_codec<PACK, NCH, float, false, true>(grid, st, a)));
+  else if (w16) DISPATCH_NCH(H, (launch_codec<PACK, NCH, bf16_t, false, true>(grid, st, a)));
   else if (x_f32) DISPATCH_NCH(H, (launch_codec<PACK, NCH, float, false>(grid, st, a)));
   else DISPATCH_NCH(H, (launch_codec<PACK, NCH, bf16_t, false>(grid, st, a)));
   return (int)hipGetLastError();

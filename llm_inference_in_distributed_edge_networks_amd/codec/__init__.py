@@ -46,12 +46,17 @@ from the UNROTATED sensitivity / relevance tables; ``group_plan: "measured"`` al
 against the quantization error the relevance pass measures per group and width in the rotated (plain) basis
 (``plan.allocate_group_bits_measured``, ``channel_group_quant_error.json``).
 
+The "native dtype" rows cross as fp32 (4 B per element) in the fp32 execution mode; ``with_native_wire(spec, "bf16" |
+"fp16" | "fp16s")`` (params key ``native_wire``) sends them as 16-bit rows instead - bf16, IEEE fp16 (overflows to Inf
+past 65504: loud) or fp16 with a per-row power-of-two scale (no finite row overflows, 8x below bf16's rounding error);
+see ``wire.py``.  BASELINE config 1 ("fp16 pass-through") is ``passthrough`` with ``"native_wire": "fp16"``.
+
 "hi"/"lo" classes: the ``k = int(ratio * S)`` least important tokens of a
 window (ascending importance, ties broken by position) are the lo class.
 """
 from . import plan  # noqa: F401  (codec.plan: the head-group bit plans)
 from .wire import (CODECS, CodecSpec, Layout, decode, encode, fake_quant, get_codec, layout, message_bytes,
-                   select_mask)
+                   select_mask, with_native_wire)
 
 __all__ = ["CODECS", "CodecSpec", "Layout", "decode", "encode", "fake_quant", "get_codec", "layout",
-           "message_bytes", "select_mask"]
+           "message_bytes", "select_mask", "with_native_wire"]

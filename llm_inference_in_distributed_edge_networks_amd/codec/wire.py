@@ -21,6 +21,22 @@ window keeps the shortest prefix of its tokens by descending importance whose ma
 the ``sum k`` lo rows (compact); its buffer (``Layout.total``) has capacity for any k and
 ``payload_bytes(sum_k)`` is what a link would carry.
 
+16-bit wire formats.  The rows a codec keeps in the activation dtype (hi or lo format ``NATIVE``: ``passthrough``,
+``ref_int4_global``, ``int4_token``, ``int8_token_keep``, ``mxfp4_keep``) cross as fp32, 4 B per element, in the fp32
+execution mode.  ``with_native_wire(spec, name)`` - a modifier of a ``CodecSpec`` like ``with_plan``, not a new codec -
+sends them in a 16-bit row format instead; the header's hi-row-format word then carries 0, 9 or 10:
+
+* ``"bf16"``  (``FMT_BF16`` = 0): round to nearest even, 2 H bytes a row; fp32's range, 8 significant bits.
+* ``"fp16"``  (``FMT_F16`` = 9): IEEE binary16, round to nearest even, 2 H bytes; subnormals and -0 kept.  A finite
+  value that rounds past 65504 encodes as +-Inf and decodes non-finite - loud, never clipped: for unbounded data (the
+  massive activations of Qwen2-class residual streams) use ``"fp16s"`` or ``"bf16"``.
+* ``"fp16s"`` (``FMT_F16S`` = 10): scaled fp16, H binary16 codes then one fp32 ``p``, 2 H + 4 bytes.  ``p = 2^k``,
+  ``k = clamp(E - 141, -112, 113)`` from the biased exponent ``E`` of the row's max-abs (p = 1 for an all-zero row,
+  p = the max-abs itself for a row holding a NaN / Inf, which decodes non-finite throughout); code =
+  ``fp16(x * 2^-k)``, decode = ``float(code) * p``.  The row's largest value lands in [2^14, 2^15), so no finite row
+  overflows, and ``|x' - x| <= max(2^-11 |x|, 2^(k - 25))``: 8x below bf16's rounding error.
+* ``"native"``: the activation dtype, as without the modifier.
+
 ``encode``/``decode`` run the gfx950 kernels of ``csrc/codec.hip`` for CUDA
 tensors and a bit-identical PyTorch implementation for CPU tensors.
 
@@ -44,10 +60,12 @@ VERSION = 1
 FMT_BF16, FMT_INT8, FMT_INT4, FMT_INT2, FMT_F32, FMT_MXFP4, FMT_MXFP8, FMT_GRP = 0, 1, 2, 3, 4, 5, 6, 7
 FMT_GRPR = 8                # FMT_GRP bytes whose codes and scales describe the Hadamard-rotated group
 MX_FORMATS = (FMT_MXFP4, FMT_MXFP8)
+FMT_F16, FMT_F16S = 9, 10   # 16-bit wires of NATIVE rows: IEEE binary16; binary16 codes + one fp32 power-of-two scale
 GRP_FORMATS = (FMT_GRP, FMT_GRPR)
 SC_TOKEN, SC_WINDOW, SC_CHANNEL, SC_NONE = 0, 1, 2, 3
 CH_MAXABS, CH_MEAN = 0, 1
 NATIVE = -1  # "keep in the activation dtype" (bf16 on GPU, fp32 in the CPU reference mode)
+NATIVE_WIRES = {"native": NATIVE, "bf16": FMT_BF16, "fp16": FMT_F16, "fp16s": FMT_F16S}   # with_native_wire
 
 
 @dataclass(frozen=True)
@@ -63,6 +81,7 @@ class CodecSpec:
     uses_ratio: bool = True      # lo class = int(ratio*S) least important tokens
     needs_importance: bool = True
     plan: tuple | None = None    # FMT_GRP / FMT_GRPR rows: bits (GROUP_BITS) of every 64-channel group (with_plan)
+    native_wire: int = NATIVE    # row format of the NATIVE classes on the wire (with_native_wire); NATIVE: the dtype's
 
 
 CODECS = {c.name: c for c in [
@@ -113,6 +132,22 @@ def with_plan(spec: CodecSpec, plan) -> CodecSpec:
     if any(b not in GROUP_BITS for b in plan):
         raise ValueError(f"group bits must be in {GROUP_BITS}, got {plan}")
     return replace(spec, plan=plan)
+
+
+def has_native_rows(spec: CodecSpec) -> bool:
+    return NATIVE in (spec.hi_fmt, spec.lo_fmt)
+
+
+def with_native_wire(spec: CodecSpec, name: str) -> CodecSpec:
+    """The codec with its NATIVE rows sent as ``name``: "native" (the activation dtype) | "bf16" | "fp16" | "fp16s"
+    (module docstring).  A codec without NATIVE rows takes "native" only."""
+    from dataclasses import replace
+    if name not in NATIVE_WIRES:
+        raise ValueError(f"native_wire must be one of {tuple(NATIVE_WIRES)}, got {name!r}")
+    if name != "native" and not has_native_rows(spec):
+        raise ValueError(f"codec {spec.name} keeps no rows in the activation dtype: native_wire {name!r} has nothing "
+                         "to apply to")
+    return spec if spec.native_wire == NATIVE_WIRES[name] else replace(spec, native_wire=NATIVE_WIRES[name])
 
 
 def get_codec(name: str) -> CodecSpec:
@@ -190,7 +225,7 @@ def layout(spec: CodecSpec, B: int, S: int, H: int, k: int, dtype: torch.dtype =
            kvar: bool = False) -> Layout:
     if H % 32:
         raise ValueError("hidden size must be a multiple of 32 for the packed formats")
-    nf = native_fmt(dtype)
+    nf = native_fmt(dtype) if spec.native_wire == NATIVE else spec.native_wire
     hi = nf if spec.hi_fmt == NATIVE else spec.hi_fmt
     lo = nf if spec.lo_fmt == NATIVE else spec.lo_fmt
     plan = None
@@ -486,6 +521,35 @@ def _bytes(t: torch.Tensor) -> torch.Tensor:
     return t.contiguous().view(torch.uint8).reshape(-1)
 
 
+# ---- scaled fp16 rows (csrc/codec.hip f16s_scale / f16_store8 / f16_load8) ---------------------------------------
+def _f16s_scale(am: torch.Tensor):
+    """(p, inv) [n] of FMT_F16S rows from their max-abs ``am`` (NaN if the row holds one), built from integer bit
+    patterns as the kernel does: p = 2^k, inv = 2^-k, k = clamp(E - 141, -112, 113) with E the biased exponent field
+    of am; am = 0 -> 1, 1; am NaN / Inf -> am, 1."""
+    bits = am.float().contiguous().view(torch.int32).to(torch.int64) & 0x7FFFFFFF
+    E = bits >> 23
+    k = (E - 141).clamp(-112, 113)
+    p = ((127 + k) << 23).to(torch.int32).view(torch.float32)
+    inv = ((127 - k) << 23).to(torch.int32).view(torch.float32)
+    one = torch.ones_like(p)
+    p, inv = torch.where(bits == 0, one, p), torch.where(bits == 0, one, inv)
+    return torch.where(E == 255, am.float(), p), torch.where(E == 255, one, inv)
+
+
+def _f16s_pack(rows: torch.Tensor) -> torch.Tensor:
+    n = rows.shape[0]
+    p, inv = _f16s_scale(rows.abs().amax(-1))
+    codes = (rows * inv[:, None]).to(torch.float16)
+    return torch.cat([codes.contiguous().view(torch.uint8).reshape(n, -1),
+                      p.contiguous().view(torch.uint8).reshape(n, 4)], 1).reshape(-1)
+
+
+def _f16s_unpack(raw: torch.Tensor, n: int, H: int) -> torch.Tensor:
+    r = raw.reshape(n, 2 * H + 4)
+    p = r[:, 2 * H:].contiguous().view(torch.float32)                     # [n, 1]
+    return r[:, :2 * H].contiguous().view(torch.float16).float() * p
+
+
 @dataclass(frozen=True)
 class RowCtx:
     """What a row format's CPU pack / unpack may need beyond the rows of one class."""
@@ -535,6 +599,10 @@ ROW_FORMATS = {
     FMT_INT8: _int_rows(FMT_INT8, 1), FMT_INT4: _int_rows(FMT_INT4, 2), FMT_INT2: _int_rows(FMT_INT2, 4),
     FMT_MXFP4: _mx_rows(FMT_MXFP4, 2), FMT_MXFP8: _mx_rows(FMT_MXFP8, 1),
     FMT_GRP: _grp_rows(False), FMT_GRPR: _grp_rows(True),
+    FMT_F16: RowFormat(lambda H, plan: 2 * H, True, lambda rows, c: _bytes(rows.to(torch.float16)),
+                       lambda raw, n, c: raw.view(torch.float16).reshape(n, c.H).float()),
+    FMT_F16S: RowFormat(lambda H, plan: 2 * H + 4, True, lambda rows, c: _f16s_pack(rows),
+                        lambda raw, n, c: _f16s_unpack(raw, n, c.H)),
 }
 
 

@@ -47,6 +47,9 @@ class Params:
     group_plan: str = "auto"                 # head-group codecs: "auto" (plans from the sensitivity / relevance tables'
                                              # error model) | "measured" (exact allocation against the measured
                                              # channel_group_quant_error.json of the relevance pass)
+    native_wire: str = "native"              # rows a codec keeps in the activation dtype cross as: "native" (that dtype:
+                                             # fp32 in the fp32 mode) | "bf16" | "fp16" | "fp16s" (codec/wire.py
+                                             # with_native_wire); BASELINE config 1 literally: passthrough + "fp16"
     lrp_engine: str = "auto"                 # relevance pass: "auto" (HIP engine on a GPU, autograd on the CPU) |
                                              # "hip" | "autograd" (AttnLRP rules as torch autograd, any device)
     output_dir: str = "."
@@ -98,6 +101,10 @@ class Params:
             raise ValueError(f"selection must be 'ratio' or 'top_rho', got {self.selection!r}")
         if self.group_plan not in ("auto", "measured"):
             raise ValueError(f"group_plan must be 'auto' or 'measured', got {self.group_plan!r}")
+        if self.native_wire != "native":
+            from .codec import wire   # a wire no codec knows, or one for a codec without native rows: ValueError
+            spec = wire.CODECS.get(self.codec) or wire.CODECS["passthrough"]
+            wire.with_native_wire(spec, self.native_wire)
 
 
 def resolve_device(p: Params) -> str:

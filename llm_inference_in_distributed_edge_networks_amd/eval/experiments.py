@@ -92,7 +92,7 @@ def importance_sweep(p: Params, default_model: str, out_name: str) -> dict:
                                     "(run Experiments/Relevance/main.py or set params['head_weights'])")
     rows = [SweepMethod(m, m, selection=p.selection) for m in methods]
     sc = SweepConfig(rows, p.layers_of_interest, p.ratios, p.codec, hw, group_relevance=_group_relevance(p),
-                     group_avg_bits=p.group_avg_bits, group_plan=p.group_plan)
+                     group_avg_bits=p.group_avg_bits, group_plan=p.group_plan, native_wire=p.native_wire)
     eng = SweepEngine(model, sc)
     state = _state(p, env, out_name)
     pb = progress_bar(len(wins), env.is_main)
@@ -124,7 +124,8 @@ def channel_sweep(p: Params, default_model: str) -> dict:
         if meth not in CHANNEL_METHODS:
             raise ValueError(f"channel sweep got non-channel method {meth!r}")
     rows = [SweepMethod(m, None, codec=m) for m in p.methods]
-    eng = SweepEngine(model, SweepConfig(rows, p.layers_of_interest, [1], p.methods[0]))
+    # the channel codecs keep no rows in the activation dtype: a non-native wire is an error (SweepEngine)
+    eng = SweepEngine(model, SweepConfig(rows, p.layers_of_interest, [1], p.methods[0], native_wire=p.native_wire))
     pb = progress_bar(len(wins), env.is_main)
     res = run_sweep(eng, _shard(batches(ids, wins, p.window_batch), env), _state(p, env, "channel"),
                     p.checkpoint_every, progress=pb.update, reduce_fn=_reduce)
@@ -178,7 +179,7 @@ def initial_experiment(p: Params) -> dict:
     """
     env, cfg, model, ids, wins, meta = _setup(p, "pythia-70m")
     sc = SweepConfig(initial_rows(p.layers_of_interest), [INITIAL_QUANT_LAYER], p.ratios, codec="int8_token_keep",
-                     ratio_scale=0.1)
+                     ratio_scale=0.1, native_wire=p.native_wire)
     eng = SweepEngine(model, sc)
     pb = progress_bar(len(wins), env.is_main)
     res = run_sweep(eng, _shard(batches(ids, wins, p.window_batch), env), _state(p, env, "exp_1"),
@@ -306,7 +307,8 @@ def pipeline_experiment(p: Params, default_model: str) -> dict:
                 log(f"{m} ratio={r}: resumed from checkpoint")
                 continue
             bcfg = BoundaryConfig(p.codec, float(r), m, hw, selection=p.selection, group_relevance=grel,
-                                  group_avg_bits=p.group_avg_bits, group_plan=p.group_plan)
+                                  group_avg_bits=p.group_avg_bits, group_plan=p.group_plan,
+                                  native_wire=p.native_wire)
             # one runtime for the whole sweep: the transport (RCCL channels / IPC slot rings) is set up once, only
             # the boundary codec changes between (method, ratio)
             if runner is None:

@@ -66,6 +66,7 @@ class SweepConfig:
     group_relevance: object = None     # head-group codecs: channel-group tables (plan source, PipelineConfig)
     group_avg_bits: float = 4.0
     group_plan: str = "auto"           # "measured": exact allocation against the measured quantization error
+    native_wire: str = "native"        # the codecs' activation-dtype rows on the wire (codec.wire.with_native_wire)
 
     def rows(self) -> list:
         out = []
@@ -80,8 +81,10 @@ class SweepEngine:
         bootstrap intervals in ``eval.stats``)."""
         self.m, self.sc = model, sc
         self._kept = [] if keep_windows else None
-        self.spec = C.get_codec(sc.codec)
+        self.spec = self._codec(sc.codec)
         self.rows = sc.rows()
+        for r in self.rows:            # a native wire for a row's codec without native rows: an error here
+            self._codec(r.codec or sc.codec)
         self.methods = [r.name for r in self.rows]
         self.layers = [int(l) for l in sc.layers]
         self.ratios = list(sc.ratios)
@@ -160,9 +163,13 @@ class SweepEngine:
         imp = {(meth, L): trackers[meth].importance(L) for meth, ls in need.items() for L in ls}
         return base, saved, imp
 
+    def _codec(self, name: str) -> C.CodecSpec:
+        """Codec ``name`` with the sweep's native wire."""
+        return C.with_native_wire(C.get_codec(name), self.sc.native_wire)
+
     def _spec_at(self, name: str, L: int) -> C.CodecSpec:
         """Codec ``name`` at the boundary after layer L (relevance-allocated group plan for head-group codecs)."""
-        spec = C.get_codec(name)
+        spec = self._codec(name)
         if not C.wire.needs_plan(spec):
             return spec
         G = self.m.cfg.hidden_size // C.wire.GROUP
@@ -184,7 +191,7 @@ class SweepEngine:
             # de-duplicate variants: key -> list of (mi, ri)
             variants: dict = {}
             for mi, row in enumerate(self.rows):
-                spec = C.get_codec(row.codec) if row.codec else self.spec
+                spec = self._codec(row.codec) if row.codec else self.spec
                 for ri, r in enumerate(self.ratios):
                     reff = float(r) * self.sc.ratio_scale
                     if C.wire.uses_kvar(spec, row.selection):
@@ -192,8 +199,11 @@ class SweepEngine:
                         variants.setdefault(key, []).append((mi, ri))
                         continue
                     k = self._k(r, S, spec)
-                    # no lo tokens and an exact hi class (reference Q1 "ratio 0"): the unquantized base
-                    if k == 0 and spec.uses_ratio and spec.hi_fmt == C.wire.NATIVE:
+                    # no lo tokens and an exact hi class (reference Q1 "ratio 0"): the unquantized base, whose
+                    # message is a pass-through in the activation dtype.  With a 16-bit native wire the hi rows are
+                    # rounded: that variant runs like any other and counts its own message's bytes.
+                    if k == 0 and spec.uses_ratio and spec.hi_fmt == C.wire.NATIVE and \
+                            spec.native_wire == C.wire.NATIVE:
                         out[mi, li, ri] = base
                         self.wire_bytes[mi, li, ri] += C.message_bytes(C.get_codec("passthrough"), B, S,
                                                                        m.cfg.hidden_size, 0.0, m.dtype)

@@ -49,14 +49,15 @@ class BoundaryConfig:
     group_relevance: object = None
     group_avg_bits: float = 4.0
     group_plan: str = "auto"      # "measured": exact allocation against the tables' measured quantization error
+    native_wire: str = "native"   # the codec's activation-dtype rows on the wire: "native" | "bf16" | "fp16" | "fp16s"
 
     @property
     def spec(self) -> C.CodecSpec:
-        return C.get_codec(self.codec)
+        return C.with_native_wire(C.get_codec(self.codec), self.native_wire)
 
     def spec_for(self, boundary: int | None, hidden: int) -> C.CodecSpec:
         """The codec of the boundary after layer ``boundary``: with its relevance-allocated group plan for the
-        head-group codecs (the tensor crossing it enters layer boundary + 1)."""
+        head-group codecs (the tensor crossing it enters layer boundary + 1) and its native wire."""
         spec = self.spec
         if boundary is None or not C.wire.needs_plan(spec):
             return spec

@@ -1,6 +1,9 @@
 """Pack / unpack time of boundary codecs against each other in one process (device events, alternating repeats).
 
     python tools/codec_bench.py --codecs rgroup,rgroup_rot --plan-bits 4 --json-out OUT/codec_bench.json
+    python tools/codec_bench.py --codecs passthrough,passthrough@bf16,passthrough@fp16,passthrough@fp16s
+
+``name@wire`` is codec ``name`` with its activation-dtype rows on the 16-bit wire ``wire`` (``with_native_wire``).
 
 Every codec packs the same activations ([B * S, H], randn with one massive channel) into its own preallocated
 message (the pack kernel alone: selection and statistics run once, before) and decodes it into a preallocated
@@ -57,7 +60,7 @@ def main():
         x = x32.to(dtype)
         runs = {}
         for n in names:
-            spec = C.get_codec(n)
+            spec = C.with_native_wire(C.get_codec(n.split("@")[0]), (n.split("@") + ["native"])[1])
             if C.wire.needs_plan(spec):
                 spec = C.wire.with_plan(spec, (a.plan_bits,) * (H // 64))
             L = C.layout(spec, B, S, H, C.wire.num_lo(spec, a.ratio, S), dtype)
