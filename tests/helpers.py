@@ -373,3 +373,285 @@ def lrp_err(name, got, ref, mag):
         return 0.0
     frac = LRP_FLOOR_FRAC[name.replace("_sum", "")]
     return float((diff / mag.clamp_min(frac * float(mag.max())))[~zero].max())
+
+
+# ---- GEMM family and LM-head NLL on ragged shapes and hard rows (test_gemm_edges*.py) -------------------------------
+# one off the 16-row MFMA group, the 64-row wave slab, the 128-row block and the 256-row four-wave tile
+GEMM_EDGE_M = [1, 2, 15, 16, 17, 63, 65, 127, 128, 129, 255, 256, 257]
+GEMM_KINDS = ["rand", "outlier", "rowmag", "cancel", "onehot", "zero_rows"]
+NLL_KINDS = ["rand", "peak12", "peak60", "far60", "flat", "shift200", "tie"]
+NLL_EDGE_R = [1, 17, 129, 257]
+U24 = 2.0 ** -24          # the unit of the GEMM measures: errors are reported in units of 2^-24 S
+GELU_LIP, SILU_LIP = 1.13, 1.1   # max |gelu'| = 1.129, max |silu'| = 1.0998
+
+
+def gemm_case(kind, M, N, K, seed):
+    """fp32 (x [M, K], w [N, K]), seeded:
+
+    rand       Gaussian x, Gaussian w / sqrt(K).
+    outlier    rand with x[:, 3] *= 1024 and x[:, K - 1] *= 256: massive channels in the first and the last 8-element
+               chunk of a K-tile row (the h3 scale is taken from them: every other channel sits 2^-8..2^-10 below it).
+    rowmag     rand with row m scaled by 2^-(m % 21): rows 2^-20 below the scale's maximum.
+    cancel     x[:, 1::2] = -x[:, 0::2] and w[:, 1::2] = w[:, 0::2] (1 + 2^-12 u), u uniform in [-1, 1]: every
+               output is the small difference of large products, |ref| <= 2^-8 sum_k |x| |w| (test_gemm_edges.py).
+    onehot     x[m, m % K] = 1 + m % 7, every other element 0; w rounded to bf16 (exact in fp16 after the power-of-two
+               scale): every output is one weight entry times a small integer, exact in fp32 and in the h3 products.
+    zero_rows  rand with rows 0, M // 2 and M - 1 all zero."""
+    g = torch.Generator().manual_seed(seed)
+    x = torch.randn(M, K, generator=g)
+    w = torch.randn(N, K, generator=g) / K ** 0.5
+    if kind in ("rand",):
+        pass
+    elif kind == "outlier":
+        x[:, 3] *= 1024.0
+        x[:, K - 1] *= 256.0
+    elif kind == "rowmag":
+        x *= (2.0 ** -(torch.arange(M) % 21).float()).view(-1, 1)
+    elif kind == "cancel":
+        x[:, 1::2] = -x[:, 0::2]
+        u = torch.rand(N, K // 2, generator=g) * 2 - 1
+        w[:, 1::2] = w[:, 0::2] * (1 + 2.0 ** -12 * u)
+    elif kind == "onehot":
+        x.zero_()
+        m = torch.arange(M)
+        x[m, m % K] = (1 + m % 7).float()
+        w = w.bfloat16().float()
+    elif kind == "zero_rows":
+        x[[0, M // 2, M - 1]] = 0.0
+    else:
+        raise ValueError(kind)
+    return x.contiguous(), w.contiguous()
+
+
+def gemm_seed(M, N, K):
+    return 9000 + 7 * M + 3 * N + K
+
+
+def nll_special_targets(V):
+    """Column 0 and V - 1, the first and the last column of the last slab of the last full 256-column tile, and one
+    column in each 64-column slab of the partial last tile (V % 256 == 128; else of the last tile's first half)."""
+    full = (V // 256) * 256
+    part = full if V % 256 else V - 256
+    return [0, V - 1, max(full - 64, 0), max(full - 1, 0), part + 5, part + 64 + 60, 63, 64]
+
+
+def nll_targets(R, V):
+    """(67 r + 5) % V; with R >= 17 rows 0..7 take ``nll_special_targets``; with R >= 129 rows 8..71 take every
+    offset 0..63 of one slab (the slab in the middle of the vocabulary)."""
+    t = (67 * torch.arange(R) + 5) % V
+    if R >= 17:
+        t[:8] = torch.tensor(nll_special_targets(V))
+    if R >= 129:
+        t[8:72] = 64 * ((V // 64) // 2) + torch.arange(64)
+    return t.long()
+
+
+def nll_case(kind, R, V, K, seed):
+    """fp32 (h [R, K], w [V, K], targets [R]); logits h @ w.T ~ N(0, 1) (h Gaussian, w Gaussian / sqrt(K)), then:
+
+    rand      unchanged.
+    peak12 / peak60  w[t_r] = c h_r / |h_r|^2, c = 12 / 60: the target logit is c, the NLL about V e^-12 / 0.
+    far60     the same row on column (t_r + V / 2) % V: maximum and target in different 64-column partials, NLL 54..66.
+    flat      w = 0: NLL = log V.
+    shift200  h[:, 0] = 20, w[:, 0] = -10: every logit near -200, the max subtraction is mandatory.
+    tie       peak12, and its weight row copied to column t_r ^ 1 (same slab) and (t_r + 192) % V (another slab): the
+              exact maximum three times (twice on the rows of the 64-offset block, whose slab is full).
+    Rows sharing a column (R > V / 67, the explicit targets) overwrite one another in row order: the later row keeps
+    its structure, the reference is computed from the weights as they are."""
+    g = torch.Generator().manual_seed(seed)
+    h = torch.randn(R, K, generator=g)
+    w = torch.randn(V, K, generator=g) / K ** 0.5
+    t = nll_targets(R, V)
+    if kind == "rand":
+        pass
+    elif kind in ("peak12", "peak60", "far60", "tie"):
+        c = 60.0 if kind in ("peak60", "far60") else 12.0
+        rows = c * h / h.pow(2).sum(-1, keepdim=True)
+        col = (t + V // 2) % V if kind == "far60" else t
+        taken = set(col.tolist())
+        for r in range(R):
+            w[col[r]] = rows[r]
+            for c2 in ([int(col[r]) ^ 1, (int(col[r]) + 192) % V] if kind == "tie" else []):
+                if c2 not in taken:              # (never over another row's target: the 64-offset block fills its slab)
+                    w[c2] = rows[r]
+    elif kind == "flat":
+        w.zero_()
+    elif kind == "shift200":
+        h[:, 0] = 20.0
+        w[:, 0] = -10.0
+    else:
+        raise ValueError(kind)
+    return h.contiguous(), w.contiguous(), t
+
+
+def nll_seed(R, V, K):
+    return 11000 + 5 * R + V % 1000 + K
+
+
+def h3_operands(x, w, two_term):
+    """The h3 operands of x @ w.T at the tensors' own power-of-two scales -> (a3, w3, alpha, sx, sw).  ``two_term``:
+    ``w`` must hold bf16 values (the single-plane weight); else the three-plane weight [N, 3K], whatever its lo plane."""
+    from llm_inference_in_distributed_edge_networks_amd.ops import reference as R
+    sx = R.h3_scale(float(x.abs().max()))
+    w3, sw = R.h3_weight(w, two_term=two_term)
+    assert w3.shape[1] == (1 if two_term else 3) * x.shape[1]
+    return R.h3_act(x, sx), w3, 1.0 / (sx * sw), sx, sw
+
+
+def h3_exact(a3, w3, alpha, rscale=None, colscale=None):
+    """The h3 arithmetic check's reference: the planes are exact inputs and fp16 x fp16 products are exact in fp32, so
+    the kernel computes alpha rscale colscale (A' @ B'^T) with fp32 accumulation only -> (that in fp64 [M, N], S =
+    |scale factors| sum_k |a'_k| |b'_k|, the GEMM's K')."""
+    from llm_inference_in_distributed_edge_networks_amd.ops import reference as R
+    terms = R.h3_terms(a3, w3)
+    A = R.h3_expand(a3, terms).double()
+    B = (torch.cat([w3, w3], -1) if terms == 2 else w3).double()
+    return scale_ref(A @ B.t(), A.abs() @ B.abs().t(), alpha, rscale, colscale) + (A.shape[1],)
+
+
+def scale_ref(p, S, alpha, rscale=None, colscale=None):
+    """(p, S) [M, N] times the product's scale factors alpha rscale[m] colscale[n] (S by their magnitudes)."""
+    f = torch.full((p.shape[0], 1), float(alpha), dtype=torch.float64)
+    if rscale is not None:
+        f = f * rscale.double().view(-1, 1)
+    if colscale is not None:
+        f = f * colscale.double().view(1, -1)
+    return p * f, S * f.abs()
+
+
+def gemm_exact(x, w, rscale=None, colscale=None):
+    """fp64 rscale colscale (x @ w.T) and S = |scales| sum_k |x_k| |w_k|: the fidelity reference of the h3 GEMMs and,
+    on bf16-rounded inputs, the reference of the bf16 GEMM."""
+    xd, wd = x.double(), w.double()
+    return scale_ref(xd @ wd.t(), xd.abs() @ wd.abs().t(), 1.0, rscale, colscale)
+
+
+def acc_cap_units(Kx):
+    """(Kx + 2) 2^-23 S in units of 2^-24 S: the standard bound on a length-Kx fp32 sum in any order with at most one
+    ulp per add (so it covers a truncating accumulator too), and two more roundings for the scale factors."""
+    return 2.0 * (Kx + 2)
+
+
+H3_DROPPED_UNITS = 8.0     # 2^-21 S: the dropped lo x lo products (2^-22) and the two planes' roundings (2^-23 each)
+
+
+def h3_lo_floor(x, w, sx, sw):
+    """The absolute floor of the lo planes [M, N] (rowmag, outlier): an element far below the scale's maximum keeps
+    absolute accuracy, not relative.  lo = fp16(s x - hi) is an fp16 subnormal when |s x - hi| < 2^-14, i.e. for every
+    |s x| < 2^-3; fp16's subnormal spacing is 2^-24, so a plane pair represents s x to within 2^-25 absolutely (and to
+    2^-22 |s x| where lo is normal - H3_DROPPED_UNITS).  Per output: 2^-25 (sum_k |w_nk| / s_x + sum_k |x_mk| / s_w)."""
+    fw = w.double().abs().sum(1).view(1, -1) / sx
+    fx = x.double().abs().sum(1).view(-1, 1) / sw
+    return 2.0 ** -25 * (fw + fx)
+
+
+def plane_out_err(ref, so):
+    """What reading a result back from h3 planes at scale ``so`` adds: 2^-22 |ref| (hi and lo roundings) + 2^-25 / so."""
+    return 2.0 ** -22 * ref.abs() + 2.0 ** -25 / so
+
+
+def add_epilogue(p, bias=None, resid=None, n_mul=1):
+    """fp64 p + bias + resid and e_out, the fp32 roundings of the epilogue itself: ``n_mul`` for the product's scale
+    factors, one per add."""
+    e = n_mul * U24 * p.abs()
+    y = p
+    if bias is not None:
+        y = y + bias.double().view(1, -1)
+        e = e + U24 * y.abs()
+    if resid is not None:
+        y = y + resid.double()
+        e = e + U24 * y.abs()
+    return y, e
+
+
+def gelu_act_eps(z, ref):
+    """The device GELU's own error on the pre-activation z: erff to a few ulp of its range [-1, 1] - an absolute
+    2^-23 on 1 + erf, times |z| / 2 - and three fp32 roundings of the result: 2^-22 (|z| + |ref|)."""
+    return 2.0 ** -22 * (z.abs() + ref.abs())
+
+
+def silu_act_eps(g, ref):
+    """The device's fast SiLU on the gate g (v_exp_f32 and v_rcp_f32 at one ulp each, the exponent's argument g log2 e
+    rounded once: a relative |g| 2^-24 on e^-g) and the products' roundings: (|g| + 6) 2^-23 |silu(g) u|."""
+    return (g.abs() + 6.0) * 2.0 ** -23 * ref.abs()
+
+
+def gemm_units(got, ref, S, e_out=None):
+    """max over the elements of (|got - ref| - e_out) / S in units of 2^-24.  An element with S = 0 (a zero row) must
+    be within e_out alone, and the output finite: otherwise the error is infinite."""
+    got, ref = got.detach().double().cpu().reshape(ref.shape), ref.double()
+    if not torch.isfinite(got).all():
+        return float("inf")
+    d = (got - ref).abs()
+    if e_out is not None:
+        d = (d - e_out).clamp_min(0.0)
+    zero = S == 0
+    if bool((d[zero] > 0).any()):
+        return float("inf")
+    if bool(zero.all()):
+        return 0.0
+    return float((d[~zero] / S[~zero]).max()) / U24
+
+
+def swiglu_ref(p, S):
+    """SwiGLU of the interleaved gate|up product p [M, N] (fp64) with the product's magnitude S propagated through the
+    activation's Lipschitz bound, delta = 1.1 |u| delta_g + |silu(g)| delta_u (first order) -> (ref [M, N/2], S_eff
+    = 1.1 |u| S_g + |silu(g)| S_u, g): a product cap of c 2^-24 S becomes c 2^-24 S_eff, and the product's own
+    rounding e_out goes the same way."""
+    from llm_inference_in_distributed_edge_networks_amd.ops import reference as R
+    g, u = R.deinterleave_gate_up(p)
+    Sg, Su = R.deinterleave_gate_up(S)
+    sg = torch.nn.functional.silu(g)
+    return sg * u, SILU_LIP * u.abs() * Sg + sg.abs() * Su, g
+
+
+def epilogue_ref(p, S, bias=None, resid=None, act=None, n_mul=1, extra=0.0):
+    """The epilogue on the fp64 product p -> (ref, S_eff, e_out): act None: p + bias + resid; "gelu": gelu(p + bias);
+    "swiglu_il": silu(gate) up of the interleaved columns.  ``extra``: a further absolute error of the product (the lo
+    planes' floor).  A product cap of c 2^-24 S becomes c 2^-24 S_eff; e_out holds the epilogue's own fp32 roundings,
+    ``extra`` and, for an activation, the device function's term - the product errors carried through the
+    activation's Lipschitz bound."""
+    if act is None:
+        ref, e = add_epilogue(p, bias, resid, n_mul)
+        return ref, S, e + extra
+    if act == "gelu":
+        z, e = add_epilogue(p, bias, None, n_mul)
+        ref = torch.nn.functional.gelu(z)
+        return ref, GELU_LIP * S, GELU_LIP * (e + extra) + gelu_act_eps(z, ref)
+    if act == "swiglu_il":
+        ref, S_eff, g = swiglu_ref(p, S)
+        e_eff = swiglu_ref(p, n_mul * U24 * p.abs() + extra)[1]
+        return ref, S_eff, e_eff + silu_act_eps(g, ref)
+    raise ValueError(act)
+
+
+# ---- LM head + cross entropy
+NLL_EPS_FN = 2.0 ** -20    # __expf / logf: every exp2 / log2 at one ulp, the arguments' scalings rounded once -
+# a relative 2^-22 on each of the two sums (the slab partials, their combination) and on the logarithm's argument
+
+
+def nll_ref(h, w, t):
+    """fp64 (nll [R], max logit, target logit, log s with s = sum exp(logit - max), A [R] = max_n sum_k |h||w|)."""
+    hd, wd = h.double(), w.double()
+    lg = hd @ wd.t()
+    mx = lg.amax(-1)
+    ls = torch.log(torch.exp(lg - mx[:, None]).sum(-1))
+    tl = lg.gather(1, t.view(-1, 1)).squeeze(1)
+    A = (hd.abs() @ wd.abs().t()).amax(-1)
+    return mx + ls - tl, mx, tl, ls, A
+
+
+def nll_cap(ref, delta_units):
+    """2 max_n delta_logit + 4 2^-24 (|max logit| + |target logit| + |log s|) + eps_fn per row, with delta_logit =
+    ``delta_units`` 2^-24 S the product cap of the path."""
+    _, mx, tl, ls, A = ref
+    return 2 * delta_units * U24 * A + 4 * U24 * (mx.abs() + tl.abs() + ls.abs()) + NLL_EPS_FN
+
+
+def nll_err(got, ref, cap):
+    """max over the rows of |got - ref| / cap (<= 1 passes) and the largest absolute error."""
+    got = got.detach().double().cpu()
+    if not torch.isfinite(got).all():
+        return float("inf"), float("inf")
+    d = (got - ref[0]).abs()
+    return float((d / cap).max()), float(d.max())
