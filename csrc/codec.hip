@@ -168,20 +168,13 @@ __device__ __forceinline__ float key_val(uint32_t k) {
 }
 
 constexpr int SEL_T = 512;
-__global__ __launch_bounds__(SEL_T) void select_sort_kernel(const float* __restrict__ imp, int S, int P, int mode,
-                                                            int k_fixed, float thr, uint32_t* __restrict__ mask_out,
-                                                            int mw, int* __restrict__ kvec) {
-  extern __shared__ __attribute__((aligned(16))) unsigned long long keys[];  // P keys, then mw mask words
-  uint32_t* mwords = (uint32_t*)(keys + P);
-  __shared__ float part[SEL_T];
-  __shared__ int cut;
-  const int b = blockIdx.x, tid = threadIdx.x;
-  const float* ib = imp + (size_t)b * S;
-  for (int i = tid; i < P; i += SEL_T)
-    keys[i] = i < S ? (((unsigned long long)ord_key(ib[i]) << 32) | (unsigned)i) : ~0ull;
-  for (int w = tid; w < mw; w += SEL_T) mwords[w] = 0u;
-  if (tid == 0) cut = S;
-  __syncthreads();
+// A window's sort key (shared by select_sort_kernel and rank_scan_kernel) and the ascending LDS bitonic sort of P keys
+// (P a power of two, the keys written and the workgroup synchronised before the call; synchronised on return).
+__device__ __forceinline__ unsigned long long sel_key(float imp, int i) {
+  return ((unsigned long long)ord_key(imp) << 32) | (unsigned)i;
+}
+__device__ __forceinline__ void bitonic_sort_keys(unsigned long long* keys, int P) {
+  const int tid = threadIdx.x;
   for (int k = 2; k <= P; k <<= 1) {
     for (int j = k >> 1; j > 0; j >>= 1) {
       for (int i = tid; i < P; i += SEL_T) {
@@ -194,6 +187,22 @@ __global__ __launch_bounds__(SEL_T) void select_sort_kernel(const float* __restr
       __syncthreads();
     }
   }
+}
+__global__ __launch_bounds__(SEL_T) void select_sort_kernel(const float* __restrict__ imp, int S, int P, int mode,
+                                                            int k_fixed, float thr, uint32_t* __restrict__ mask_out,
+                                                            int mw, int* __restrict__ kvec) {
+  extern __shared__ __attribute__((aligned(16))) unsigned long long keys[];  // P keys, then mw mask words
+  uint32_t* mwords = (uint32_t*)(keys + P);
+  __shared__ float part[SEL_T];
+  __shared__ int cut;
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const float* ib = imp + (size_t)b * S;
+  for (int i = tid; i < P; i += SEL_T)
+    keys[i] = i < S ? sel_key(ib[i], i) : ~0ull;
+  for (int w = tid; w < mw; w += SEL_T) mwords[w] = 0u;
+  if (tid == 0) cut = S;
+  __syncthreads();
+  bitonic_sort_keys(keys, P);
   int kk = k_fixed;
   if (mode == 1) {
     // descending value i = keys[S-1-i]; thread t owns the contiguous run [t*C, t*C + C) of descending positions
@@ -346,6 +355,25 @@ __device__ __forceinline__ void load_row8(const bf16_t* __restrict__ src, int H,
 }
 
 __device__ __forceinline__ float qround(float t, float qmax, float qmin) { return fminf(fmaxf(rintf(t), qmin), qmax); }
+
+// The integer rows' arithmetic in the per-token and per-window scale modes, one definition for pack_kernel,
+// unpack_kernel and fork_kernel (which quantizes and dequantizes a row with no bytes in between): the per-token scale
+// and its inverse from the row's max|x|, a value's code (an integer-valued float inside the format's range; the wire
+// carries (int)code, so a -0 crosses as 0), and a code's value.
+__device__ __forceinline__ float tok_scale(float am, int qmax) { return am / (float)qmax; }
+__device__ __forceinline__ float tok_inv(float am, float s) { return am > 0.f ? 1.f / s : 0.f; }
+__device__ __forceinline__ float qmin_of(int scale_mode, int qmax) {
+  return scale_mode == SC_WINDOW ? -(float)(qmax + 1) : -(float)qmax;
+}
+__device__ __forceinline__ float tok_code(float xv, float inv, float qmaxf, float qminf) {
+  return qround(xv * inv, qmaxf, qminf);
+}
+// reference Q1: round(clamp(x / m * 7, -8, 7))
+__device__ __forceinline__ float win_code(float xv, float mul, float qmaxf, float qminf) {
+  return mul > 0.f ? rintf(fminf(fmaxf(xv / mul * qmaxf, qminf), qmaxf)) : 0.f;
+}
+__device__ __forceinline__ float tok_value(float qf, float s) { return qf * s; }
+__device__ __forceinline__ float win_value(float qf, int qmax, float s) { return qf / (float)qmax * s; }   // q / 7 * m
 
 typedef __attribute__((ext_vector_type(2))) short s16x2_t;
 
@@ -646,15 +674,15 @@ __global__ __launch_bounds__(256) void pack_kernel(CodecArgs a) {
 #pragma unroll
         for (int e = 0; e < 8; ++e) amb = umax(amb, abs_bits(v[c][e]));
       const float am = __uint_as_float(wave_umax(amb));   // NaN / Inf if the row holds one: s non-finite
-      const float s = am / (float)qmax;
+      const float s = tok_scale(am, qmax);
       if (lane == 0) scales[row] = s;
-      inv = am > 0.f ? 1.f / s : 0.f;
+      inv = tok_inv(am, s);
     } else if (a.scale_mode == SC_WINDOW) {
       mul = scales[b];  // max|x| over the window's lo rows
     }
   }
   const float qmaxf = (float)qmax;
-  const float qminf = a.scale_mode == SC_WINDOW ? -(float)(qmax + 1) : -(float)qmax;
+  const float qminf = qmin_of(a.scale_mode, qmax);
   float inv16 = 1.f;   // FMT_F16S: 1 / p of the row (FMT_F16: 1, an exact multiply)
   if constexpr (W16) {
     if (fmt == FMT_F16S) {
@@ -708,10 +736,9 @@ __global__ __launch_bounds__(256) void pack_kernel(CodecArgs a) {
       const float xv = v[c][e];
       float t;
       if (a.scale_mode == SC_TOKEN) {
-        t = qround(xv * inv, qmaxf, qminf);
+        t = tok_code(xv, inv, qmaxf, qminf);
       } else if (a.scale_mode == SC_WINDOW) {
-        // reference Q1: round(clamp(x / m * 7, -8, 7))
-        t = mul > 0.f ? rintf(fminf(fmaxf(xv / mul * qmaxf, qminf), qmaxf)) : 0.f;
+        t = win_code(xv, mul, qmaxf, qminf);
       } else {
         const float sc = scales[(size_t)b * a.H + col + e];
         if (a.ch_kind == CH_MEAN || qmax == 1) {
@@ -838,14 +865,159 @@ __global__ __launch_bounds__(256) void unpack_kernel(CodecArgs a) {
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
       const float qf = (float)q[e];
-      if (a.scale_mode == SC_TOKEN) o[e] = qf * s;
-      else if (a.scale_mode == SC_WINDOW) o[e] = qf / (float)qmax * s;            // reference: q / 7 * m
+      if (a.scale_mode == SC_TOKEN) o[e] = tok_value(qf, s);
+      else if (a.scale_mode == SC_WINDOW) o[e] = win_value(qf, qmax, s);
       else {
         const float sc = scales[(size_t)b * a.H + col + e];
         o[e] = (a.ch_kind == CH_MEAN || qmax == 1) ? qf * sc : qf * sc / (float)qmax;
       }
     }
     store8(out + col, o);
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
+// Fork (the sweep's step between prefix and suffix): one hidden state x [B S, H] in, the receiver-side activations of
+// V (importance source, k) variants of ONE codec out, stacked: out[(v B + b) S + j] is what unpack_kernel would write
+// for token j of window b from the message pack_kernel builds with the k_v least important tokens of source src_v in
+// the lo class - bit for bit, through the same device functions, with no message in between.  Three launches:
+//   row_absmax_kernel (SC_WINDOW only): the bits of max|x| of every row, one wave per row.
+//   rank_scan_kernel : one workgroup per (source, window) sorts select_sort_kernel's keys once for all k and writes
+//                      rank[src][b][j], token j's position in the ascending order: token j is lo in variant v
+//                      <=> rank[src_v][b][j] < k_v.  SC_WINDOW: the window scale of variant v, the max|x| over its lo
+//                      rows (channel_stats only_lo + rowmax), is the k_v-th inclusive prefix umax of the rows' max-abs
+//                      bits along that order (an LDS block scan; maxima of abs_bits patterns: order-independent,
+//                      NaN-propagating), 0 for k_v = 0: wscale[v][b].
+//   fork_kernel      : one wave per token row loads the row once (load_row8), takes its max-abs once and loops over
+//                      the variants: class -> format, qmax, scale (per token from the row max, per window from
+//                      wscale) -> codes -> values in registers -> one row store per variant.  Native rows are copied.
+// Row formats: the activation dtype's native format, INT8, INT4, INT2; scale modes SC_TOKEN and SC_WINDOW; fixed k.
+// The variant table tab[v] = (src_v, k_v) is int32 on the device; V <= FORK_MAXV per launch.
+constexpr int FORK_MAXV = 64;
+// The fork kernels are compiled without gfx950's packed fp32 instructions (v_pk_mul_f32 and kin): every multiply of a
+// row is its own scalar-per-lane instruction.  Device pass only - the host pass has no such feature to switch.
+#if defined(__HIP_DEVICE_COMPILE__)
+#define FORK_NO_PK_F32 __attribute__((target("no-packed-fp32-ops")))
+#else
+#define FORK_NO_PK_F32
+#endif
+
+template <int NCH, class T>
+__global__ FORK_NO_PK_F32 __launch_bounds__(256) void row_absmax_kernel(const T* __restrict__ x, uint32_t* __restrict__ amax,
+                                                         int rows, int H) {
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= rows) return;
+  float v[NCH][8];
+  load_row8<NCH>(x + (size_t)row * H, H, v);
+  uint32_t amb = 0;
+#pragma unroll
+  for (int c = 0; c < NCH; ++c) amb = umax(amb, umax8(v[c]));
+  amb = wave_umax(amb);
+  if ((threadIdx.x & 63) == 0) amax[row] = amb;
+}
+
+// grid (sources, B).  imp [nsrc, B, S] (null: one source in position order - every variant has k in {0, S});
+// rank [nsrc, B, S]; amax [B, S] row max-abs bits (null unless SC_WINDOW); wscale [V, B].
+// LDS: P keys, then S prefix words when amax is given.
+__global__ FORK_NO_PK_F32 __launch_bounds__(SEL_T) void rank_scan_kernel(const float* __restrict__ imp, int B, int S, int P,
+                                                          int* __restrict__ rank, const uint32_t* __restrict__ amax,
+                                                          const int* __restrict__ tab, int V,
+                                                          float* __restrict__ wscale) {
+  extern __shared__ __attribute__((aligned(16))) unsigned long long keys[];
+  uint32_t* pm = (uint32_t*)(keys + P);
+  __shared__ uint32_t part[SEL_T];
+  const int src = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
+  const size_t wb = ((size_t)src * B + b) * S;
+  for (int i = tid; i < P; i += SEL_T)
+    keys[i] = i < S ? (imp ? sel_key(imp[wb + i], i) : (unsigned long long)i) : ~0ull;
+  __syncthreads();
+  if (imp) bitonic_sort_keys(keys, P);
+  for (int p = tid; p < S; p += SEL_T) rank[wb + (int)(keys[p] & 0xFFFFFFFFu)] = p;
+  if (!amax) return;
+  // inclusive prefix umax of the rows' max-abs bits in sorted order; thread t owns the run [t C, t C + C)
+  for (int p = tid; p < S; p += SEL_T) pm[p] = amax[(size_t)b * S + (int)(keys[p] & 0xFFFFFFFFu)];
+  __syncthreads();
+  const int C = (S + SEL_T - 1) / SEL_T;
+  const int i0 = tid * C;
+  uint32_t run = 0;
+  for (int e = 0; e < C && i0 + e < S; ++e) run = umax(run, pm[i0 + e]);
+  part[tid] = run;
+  __syncthreads();
+  for (int off = 1; off < SEL_T; off <<= 1) {  // Hillis-Steele inclusive scan of the run maxima
+    const uint32_t o = tid >= off ? part[tid - off] : 0u;
+    __syncthreads();
+    part[tid] = umax(part[tid], o);
+    __syncthreads();
+  }
+  uint32_t acc = tid ? part[tid - 1] : 0u;
+  for (int e = 0; e < C && i0 + e < S; ++e) {
+    acc = umax(acc, pm[i0 + e]);
+    pm[i0 + e] = acc;
+  }
+  __syncthreads();
+  for (int v = tid; v < V; v += SEL_T) {
+    if (tab[2 * v] != src) continue;
+    const int k = min(tab[2 * v + 1], S);
+    wscale[(size_t)v * B + b] = k > 0 ? __uint_as_float(pm[k - 1]) : 0.f;
+  }
+}
+
+struct ForkArgs {
+  const void* x; void* out;
+  const int* rank;              // [nsrc, B, S]; null: no variant has 0 < k < S
+  const float* wscale;          // [V, B] (SC_WINDOW)
+  const int* tab;               // [V, 2] (source, k)
+  int B, S, H, V;
+  int hi_fmt, lo_fmt, scale_mode, qmax_hi, qmax_lo;
+};
+
+template <int NCH, class T>
+__global__ FORK_NO_PK_F32 __launch_bounds__(256) void fork_kernel(ForkArgs a) {
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= a.B * a.S) return;
+  const int lane = threadIdx.x & 63;
+  const int b = row / a.S, j = row - b * a.S;
+  float v[NCH][8];
+  load_row8<NCH>((const T*)a.x + (size_t)row * a.H, a.H, v);
+  uint32_t amb = 0;
+#pragma unroll
+  for (int c = 0; c < NCH; ++c) amb = umax(amb, umax8(v[c]));
+  const float am = __uint_as_float(wave_umax(amb));   // NaN / Inf if the row holds one
+  const size_t rows = (size_t)a.B * a.S;
+  for (int vi = 0; vi < a.V; ++vi) {
+    const int src = a.tab[2 * vi], k = a.tab[2 * vi + 1];
+    const bool is_lo = a.rank ? a.rank[((size_t)src * a.B + b) * a.S + j] < k : k >= a.S;
+    const int fmt = is_lo ? a.lo_fmt : a.hi_fmt, qmax = is_lo ? a.qmax_lo : a.qmax_hi;
+    T* out = (T*)a.out + ((size_t)vi * rows + row) * a.H;
+    if (fmt == FMT_BF16 || fmt == FMT_F32) {   // native row: the activation's own bits
+#pragma unroll
+      for (int c = 0; c < NCH; ++c) {
+        const int col = (c * 64 + lane) * 8;
+        if (col < a.H) store8(out + col, v[c]);
+      }
+      continue;
+    }
+    const float qmaxf = (float)qmax, qminf = qmin_of(a.scale_mode, qmax);
+    float s, inv = 0.f;
+    if (a.scale_mode == SC_TOKEN) {
+      s = tok_scale(am, qmax);
+      inv = tok_inv(am, s);
+    } else {
+      s = a.wscale[(size_t)vi * a.B + b];
+    }
+#pragma unroll
+    for (int c = 0; c < NCH; ++c) {
+      const int col = (c * 64 + lane) * 8;
+      if (col >= a.H) continue;
+      float o[8];
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        // (float)(int)code: the code as the message carries it
+        if (a.scale_mode == SC_TOKEN) o[e] = tok_value((float)(int)tok_code(v[c][e], inv, qmaxf, qminf), s);
+        else o[e] = win_value((float)(int)win_code(v[c][e], s, qmaxf, qminf), qmax, s);
+      }
+      store8(out + col, o);
+    }
   }
 }
 
@@ -1107,5 +1279,55 @@ EDGE_API int edge_group_quant_err(const void* x, const float* dx, float* err, fl
   const int n = H / 64 * 2 * QE_NW;
   const long long total = (long long)B * n;
   group_quant_err_sum_kernel<<<(unsigned)((total + 255) / 256), 256, 0, st>>>(ws, err, chunks, n, total);
+  return (int)hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------
+// edge_fake_quant_fork: x [B S, H] -> out [V B S, H] (the activation dtype), see fork_kernel.  imp [nsrc, B, S] fp32
+// (nsrc = 0: null, every k in {0, S}); tab [V, 2] int32 on the device with 0 <= source < max(nsrc, 1); workspaces
+// rank [max(nsrc, 1) B S] int32, amax [B S] u32 and wscale [V B] fp32 (the last two for SC_WINDOW only).
+template <int NCH, class T>
+static void launch_fork(dim3 grid, hipStream_t st, const ForkArgs& a, uint32_t* amax) {
+  if (amax) hipLaunchKernelGGL((row_absmax_kernel<NCH, T>), grid, dim3(256), 0, st, (const T*)a.x, amax, a.B * a.S, a.H);
+  else hipLaunchKernelGGL((fork_kernel<NCH, T>), grid, dim3(256), 0, st, a);
+}
+
+static bool fork_fmt_ok(int fmt, int qmax, int native) {
+  return fmt == native || (fmt == FMT_INT8 && qmax == 127) || (fmt == FMT_INT4 && qmax == 7) ||
+         (fmt == FMT_INT2 && qmax == 1);
+}
+
+EDGE_API int edge_fake_quant_fork(const void* x, void* out, const float* imp, int nsrc, const int* tab, int V,
+                                  int* rank, void* amax, float* wscale, int B, int S, int H, int hi_fmt, int lo_fmt,
+                                  int scale_mode, int qmax_hi, int qmax_lo, int x_f32, hipStream_t st) {
+  const int native = x_f32 ? FMT_F32 : FMT_BF16;
+  if (H <= 0 || H % 32 || S <= 0 || S > 8192 || B < 0 || V <= 0 || V > FORK_MAXV || nsrc < 0 || (nsrc > 0 && !imp) ||
+      (scale_mode != SC_TOKEN && scale_mode != SC_WINDOW) || !fork_fmt_ok(hi_fmt, qmax_hi, native) ||
+      !fork_fmt_ok(lo_fmt, qmax_lo, native) || (long long)B * S > 0x7fffffffll)
+    return (int)hipErrorInvalidValue;
+  const bool window = scale_mode == SC_WINDOW;
+  if (window && (!amax || !wscale)) return (int)hipErrorInvalidValue;
+  if ((nsrc > 0 || window) && !rank) return (int)hipErrorInvalidValue;
+  ForkArgs a;
+  a.x = x; a.out = out; a.rank = nsrc > 0 || window ? rank : nullptr; a.wscale = wscale; a.tab = tab;
+  a.B = B; a.S = S; a.H = H; a.V = V;
+  a.hi_fmt = hi_fmt; a.lo_fmt = lo_fmt; a.scale_mode = scale_mode; a.qmax_hi = qmax_hi; a.qmax_lo = qmax_lo;
+  if (B == 0) { DISPATCH_NCH(H, (void)0); return 0; }
+  const dim3 grid((unsigned)(((long long)B * S + 3) / 4));
+  if (window) {
+    if (x_f32) DISPATCH_NCH(H, (launch_fork<NCH, float>(grid, st, a, (uint32_t*)amax)));
+    else DISPATCH_NCH(H, (launch_fork<NCH, bf16_t>(grid, st, a, (uint32_t*)amax)));
+  }
+  if (a.rank) {
+    int P = 1;
+    while (P < S) P <<= 1;
+    const size_t lds = (size_t)P * 8 + (window ? (size_t)S * 4 : 0);
+    if (lds > 65536) (void)hipFuncSetAttribute((const void*)rank_scan_kernel,
+                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipLaunchKernelGGL(rank_scan_kernel, dim3(nsrc > 0 ? nsrc : 1, B), dim3(SEL_T), lds, st, imp, B, S, P, rank,
+                       window ? (const uint32_t*)amax : nullptr, tab, V, wscale);
+  }
+  if (x_f32) DISPATCH_NCH(H, (launch_fork<NCH, float>(grid, st, a, nullptr)));
+  else DISPATCH_NCH(H, (launch_fork<NCH, bf16_t>(grid, st, a, nullptr)));
   return (int)hipGetLastError();
 }

@@ -51,12 +51,17 @@ The "native dtype" rows cross as fp32 (4 B per element) in the fp32 execution mo
 past 65504: loud) or fp16 with a per-row power-of-two scale (no finite row overflows, 8x below bf16's rounding error);
 see ``wire.py``.  BASELINE config 1 ("fp16 pass-through") is ``passthrough`` with ``"native_wire": "fp16"``.
 
+``fake_quant_fork(x, spec, B, S, variants, importances)`` is ``fake_quant`` for a whole list of (importance source, k)
+variants of one codec at once - the sweep's step between the shared prefix and the stacked suffix: one sort per
+source, one read of ``x``, one write per variant, bit-identical to the per-variant round trip (``fork_supported``: the
+native / int8 / int4 / int2 codecs with per-token or per-window scales, ratio selection, native wire).
+
 "hi"/"lo" classes: the ``k = int(ratio * S)`` least important tokens of a
 window (ascending importance, ties broken by position) are the lo class.
 """
 from . import plan  # noqa: F401  (codec.plan: the head-group bit plans)
-from .wire import (CODECS, CodecSpec, Layout, decode, encode, fake_quant, get_codec, layout, message_bytes,
-                   select_mask, with_native_wire)
+from .wire import (CODECS, CodecSpec, Layout, decode, encode, fake_quant, fake_quant_fork, fork_supported, get_codec,
+                   layout, message_bytes, select_mask, with_native_wire)
 
-__all__ = ["CODECS", "CodecSpec", "Layout", "decode", "encode", "fake_quant", "get_codec", "layout",
-           "message_bytes", "select_mask", "with_native_wire"]
+__all__ = ["CODECS", "CodecSpec", "Layout", "decode", "encode", "fake_quant", "fake_quant_fork", "fork_supported",
+           "get_codec", "layout", "message_bytes", "select_mask", "with_native_wire"]

@@ -809,3 +809,78 @@ def message_k(msg: torch.Tensor, L: Layout) -> torch.Tensor:
 def message_payload(msg: torch.Tensor, L: Layout) -> int:
     """Bytes a link carries for this message (host sync for a variable-k message)."""
     return L.total if not L.kvar else L.payload_bytes(int(message_k(msg, L).sum()))
+
+
+# --------------------------------------------------------------------------------------------
+# Fork: one hidden state -> the receiver-side activations of all (source, k) variants of one codec, stacked
+FORK_MAXV = 64              # variants per launch (csrc/codec.hip FORK_MAXV); longer lists are split here
+_FORK_ROWS = ((NATIVE, 0), (FMT_INT8, 127), (FMT_INT4, 7), (FMT_INT2, 1))
+
+
+def fork_supported(spec: CodecSpec, selection: str = "ratio") -> bool:
+    """``fake_quant_fork`` serves this codec: native / int8 / int4 / int2 rows with per-token or per-window scales,
+    fixed k, NATIVE rows in the activation dtype (the codecs the sweeps run: ref_int4_global, int4_token, int8_token,
+    int8_token_keep, mixed_int4_int8, mixed_int2_int8).  Everything else keeps the per-variant ``fake_quant``."""
+    uses_kvar(spec, selection)       # an unknown selection: ValueError
+    return (selection == "ratio" and spec.native_wire == NATIVE
+            and spec.scale_mode in (SC_TOKEN, SC_WINDOW)
+            and (spec.hi_fmt, spec.qmax_hi) in _FORK_ROWS and (spec.lo_fmt, spec.qmax_lo) in _FORK_ROWS)
+
+
+def _fork_gpu(x, spec, B, S, variants, importances, out):
+    H, dev, nsrc = x.shape[-1], x.device, len(importances)
+    L = layout(spec, B, S, H, 0, x.dtype)             # the resolved row formats
+    imp = None
+    if nsrc:
+        imp = importances[0] if nsrc == 1 else torch.stack([i.reshape(B, S) for i in importances])
+        imp = imp.float().contiguous()
+    window = spec.scale_mode == SC_WINDOW
+    rank = torch.empty(max(nsrc, 1) * B * S, dtype=torch.int32, device=dev) if nsrc or window else None
+    amax = torch.empty(B * S, dtype=torch.int32, device=dev) if window else None
+    for v0 in range(0, len(variants), FORK_MAXV):
+        vs = tuple(variants[v0:v0 + FORK_MAXV])
+        tab = _dev_const(("fork_tab", vs), dev, lambda: torch.tensor(vs, dtype=torch.int32))
+        wscale = torch.empty(len(vs) * B, dtype=torch.float32, device=dev) if window else None
+        call("edge_fake_quant_fork", ptr(x), ptr(out[v0 * B * S:]), ptr(imp), nsrc, ptr(tab), len(vs), ptr(rank),
+             ptr(amax), ptr(wscale), B, S, H, L.hi_fmt, L.lo_fmt, spec.scale_mode, spec.qmax_hi, spec.qmax_lo,
+             int(x.dtype == torch.float32), stream())
+    return out
+
+
+def fake_quant_fork(x: torch.Tensor, spec: CodecSpec, B: int, S: int, variants, importances=(), out=None):
+    """``fake_quant`` of ``x`` ([B*S, H]) for every variant at once: (x_hat [V*B*S, H], message bytes per variant).
+
+    ``variants``: a list of ``(source, k)`` - the lo class of variant v is the ``k`` least important tokens of every
+    window by ``importances[source]`` ([B, S]); ``source`` None needs ``k`` in {0, S} (no importance read, as for any
+    variant with such a ``k``).  Rows ``[v*B*S, (v+1)*B*S)`` of the result are bit for bit
+    ``fake_quant(x, spec, B, S, importance=importances[source], k=k)[0]``, which is what runs for CPU tensors; CUDA
+    tensors run one sort per source, one read of ``x`` and one write per variant (csrc/codec.hip fork_kernel) with no
+    message in between.  ``out``: a contiguous [V*B*S, H] tensor of ``x``'s dtype to write into."""
+    if not fork_supported(spec):
+        raise ValueError(f"codec {spec.name} (native wire {spec.native_wire}) is not served by fake_quant_fork")
+    H, V = x.shape[-1], len(variants)
+    vs = []
+    for src, k in variants:
+        k = max(0, min(S, int(k))) if spec.uses_ratio else 0
+        if 0 < k < S and src is None:
+            raise ValueError(f"codec {spec.name} with 0 < k < S needs token importance")
+        if src is not None and not 0 <= src < len(importances):
+            raise ValueError(f"variant source {src} outside the {len(importances)} importances")
+        vs.append((src, k))
+    nbytes = [layout(spec, B, S, H, k, x.dtype).total for _, k in vs]
+    if out is None:
+        out = torch.empty(V * B * S, H, dtype=x.dtype, device=x.device)
+    elif out.shape != (V * B * S, H) or out.dtype != x.dtype or not out.is_contiguous():
+        raise ValueError("out must be a contiguous [V*B*S, H] tensor of the activations' dtype")
+    if not V:
+        return out, nbytes
+    if x.is_cuda:
+        if x.dtype not in (torch.bfloat16, torch.float32):
+            raise TypeError("GPU boundary codec expects bf16 or fp32 activations")
+        _fork_gpu(x.contiguous(), spec, B, S, [(0 if src is None else src, k) for src, k in vs], list(importances), out)
+    else:
+        for v, (src, k) in enumerate(vs):
+            out[v * B * S:(v + 1) * B * S] = fake_quant(x, spec, B, S, k=k,
+                                                        importance=None if src is None else importances[src])[0]
+    return out, nbytes
+

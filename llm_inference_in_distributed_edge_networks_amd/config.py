@@ -50,6 +50,8 @@ class Params:
     native_wire: str = "native"              # rows a codec keeps in the activation dtype cross as: "native" (that dtype:
                                              # fp32 in the fp32 mode) | "bf16" | "fp16" | "fp16s" (codec/wire.py
                                              # with_native_wire); BASELINE config 1 literally: passthrough + "fp16"
+    sweep_fork: bool = False                 # sweeps: all (method, ratio) variants of a boundary layer from one
+                                             # codec.fake_quant_fork pass (bit-identical to the per-variant path)
     lrp_engine: str = "auto"                 # relevance pass: "auto" (HIP engine on a GPU, autograd on the CPU) |
                                              # "hip" | "autograd" (AttnLRP rules as torch autograd, any device)
     output_dir: str = "."

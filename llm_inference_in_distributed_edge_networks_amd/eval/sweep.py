@@ -67,6 +67,7 @@ class SweepConfig:
     group_avg_bits: float = 4.0
     group_plan: str = "auto"           # "measured": exact allocation against the measured quantization error
     native_wire: str = "native"        # the codecs' activation-dtype rows on the wire (codec.wire.with_native_wire)
+    fork: bool = False                 # fake-quantize the variants of a boundary layer with codec.fake_quant_fork
 
     def rows(self) -> list:
         out = []
@@ -180,6 +181,41 @@ class SweepEngine:
     def _k(self, ratio, S, spec=None):
         return C.wire.num_lo(spec or self.spec, float(ratio) * self.sc.ratio_scale, S)
 
+    def _fake_quant(self, key, h, imp, L, B, S):
+        """One variant's receiver-side activations and message bytes (the per-variant path)."""
+        src, kk, cname = key[0], key[1], key[-1]
+        spec = self._spec_at(cname, L)
+        im = None if src == "all" else imp[src]
+        if kk == "top_rho":
+            return C.fake_quant(h, spec, B, S, key[2], importance=im, selection="top_rho")
+        return C.fake_quant(h, spec, B, S, importance=im, k=kk)
+
+    def _fork_chunk(self, chunk, variants, h, imp, L, li, B, S):
+        """The chunk's stacked variants, in the chunk's order, written straight into one tensor: every run of
+        consecutive keys of one codec that ``fork_supported`` accepts is one ``fake_quant_fork`` over the run's
+        distinct importance sources; the other keys take ``_fake_quant``."""
+        x = torch.empty(len(chunk) * B * S, h.shape[-1], dtype=h.dtype, device=h.device)
+        v0 = 0
+        while v0 < len(chunk):
+            cname = chunk[v0][-1]
+            spec = self._spec_at(cname, L)
+            v1 = v0 + 1
+            if chunk[v0][1] == "top_rho" or not C.fork_supported(spec):
+                xq, nb = self._fake_quant(chunk[v0], h, imp, L, B, S)
+                x[v0 * B * S:v1 * B * S].copy_(xq)
+                nbytes = [nb]
+            else:
+                while v1 < len(chunk) and chunk[v1][-1] == cname and chunk[v1][1] != "top_rho":
+                    v1 += 1
+                srcs = list(dict.fromkeys(key[0] for key in chunk[v0:v1] if key[0] != "all"))
+                vs = [(None if key[0] == "all" else srcs.index(key[0]), key[1]) for key in chunk[v0:v1]]
+                _, nbytes = C.fake_quant_fork(h, spec, B, S, vs, [imp[s] for s in srcs], out=x[v0 * B * S:v1 * B * S])
+            for key, nb in zip(chunk[v0:v1], nbytes):
+                for (mi, ri) in variants[key]:
+                    self.wire_bytes[mi, li, ri] += nb
+            v0 = v1
+        return x
+
     def run_batch(self, batch: WindowBatch) -> torch.Tensor:
         """Returns per-window NLL [M, Lc, R, B] for this batch (also accumulated)."""
         m, B, S = self.m, batch.B, batch.S
@@ -215,20 +251,17 @@ class SweepEngine:
             per_fork = max(1, self.sc.max_fork_tokens // (B * S))
             for c0 in range(0, len(keys), per_fork):
                 chunk = keys[c0:c0 + per_fork]
-                xs = []
-                for key in chunk:
-                    src, kk, cname = key[0], key[1], key[-1]
-                    spec = self._spec_at(cname, L)
-                    im = None if src == "all" else imp[src]
-                    if kk == "top_rho":
-                        xq, nbytes = C.fake_quant(saved[L], spec, B, S, key[2], importance=im, selection="top_rho")
-                    else:
-                        xq, nbytes = C.fake_quant(saved[L], spec, B, S, importance=im, k=kk)
-                    xs.append(xq)
-                    for (mi, ri) in variants[key]:
-                        self.wire_bytes[mi, li, ri] += nbytes
                 V = len(chunk)
-                x = torch.cat(xs, 0)
+                if self.sc.fork:
+                    x = self._fork_chunk(chunk, variants, saved[L], imp, L, li, B, S)
+                else:
+                    xs = []
+                    for key in chunk:
+                        xq, nbytes = self._fake_quant(key, saved[L], imp, L, B, S)
+                        xs.append(xq)
+                        for (mi, ri) in variants[key]:
+                            self.wire_bytes[mi, li, ri] += nbytes
+                    x = torch.cat(xs, 0)
                 off = (torch.arange(V, device=batch.rows.device) * (B * S)).repeat_interleave(batch.rows.numel())
                 rows = batch.rows.repeat(V) + off
                 for i in range(L + 1, m.cfg.num_layers):

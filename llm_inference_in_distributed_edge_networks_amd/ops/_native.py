@@ -97,6 +97,8 @@ _SIGS = {
     # measured quantization error of the head groups (csrc/codec.hip): the kernel, and the row chunks its workspace has
     "edge_group_quant_err": [c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_p],
     "edge_group_quant_err_chunks": [c_i],
+    # fork of one hidden state into all (source, k) variants of a codec (csrc/codec.hip fork_kernel)
+    "edge_fake_quant_fork": [c_p, c_p, c_p, c_i, c_p, c_i, c_p, c_p, c_p] + [c_i] * 9 + [c_p],
     # debug (csrc/debug.hip): LDS + register-file poison before every kernel under EDGE_POISON=2
     "edge_poison_lds": [c_p],
     "edge_poison_lds_bytes": [],

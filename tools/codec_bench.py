@@ -9,6 +9,10 @@ Every codec packs the same activations ([B * S, H], randn with one massive chann
 message (the pack kernel alone: selection and statistics run once, before) and decodes it into a preallocated
 tensor; a repeat times ``--iters`` back-to-back calls of one direction
 between two events, and the codecs alternate within every repeat so that clock and neighbour drift hit all alike.
+``--fork-variants 10,40`` times something else: the sweep's step between prefix and suffix for V variants of each
+codec (V / 10 importance sources x ratios 0.1 .. 1.0) - V ``fake_quant`` calls plus ``torch.cat`` against one
+``fake_quant_fork`` into a preallocated tensor - after checking that both give the same bits.
+
 Reported per codec, dtype and direction: the median over the repeats, their min - max spread, and the ratio of
 the medians to the first codec's.  Needs a GPU: there is no CPU fallback (a CPU time says nothing here)."""
 import argparse
@@ -34,6 +38,38 @@ def timed(fn, iters):
     return a.elapsed_time(b) * 1e3 / iters       # us per call
 
 
+def fork_bench(a, names, x32, out):
+    """Per-variant path against the fork; appended to out["results"] as direction "per_variant" / "fork"."""
+    B, S, H = a.batch, a.seq, a.hidden
+    g = torch.Generator("cuda").manual_seed(1)
+    for dtype in (torch.float32, torch.bfloat16):
+        x = x32.to(dtype)
+        for n in names:
+            spec = C.get_codec(n)
+            for V in (int(v) for v in a.fork_variants.split(",")):
+                imps = [torch.rand(B, S, generator=g, device="cuda") for _ in range(max(1, V // 10))]
+                variants = [(v % len(imps), int((1 + v // len(imps) % 10) / 10 * S)) for v in range(V)]
+                y = torch.empty(V * B * S, H, dtype=dtype, device="cuda")
+                fns = {"per_variant": lambda: torch.cat([C.fake_quant(x, spec, B, S, importance=imps[s], k=k)[0]
+                                                         for s, k in variants]),
+                       "fork": lambda: C.fake_quant_fork(x, spec, B, S, variants, imps, out=y)[0]}
+                bits = torch.int32 if dtype == torch.float32 else torch.int16
+                if not torch.equal(fns["per_variant"]().view(bits), fns["fork"]().view(bits)):
+                    raise SystemExit(f"{n} {dtype} V={V}: the fork differs from the per-variant path")
+                t = {k: [] for k in fns}
+                for _ in range(a.repeats):
+                    for k, fn in fns.items():
+                        t[k].append(timed(fn, a.iters))
+                base = statistics.median(t["per_variant"])
+                for k in fns:
+                    med = statistics.median(t[k])
+                    out["results"].append({"dtype": str(dtype).split(".")[-1], "codec": n, "variants": V,
+                                           "direction": k, "median_us": round(med, 2), "min_us": round(min(t[k]), 2),
+                                           "max_us": round(max(t[k]), 2), "ratio_to_first": round(med / base, 4)})
+                    print(f"{str(dtype).split('.')[-1]:8s} {n:18s} V={V:3d} {k:11s} median {med:10.2f} us  "
+                          f"[{min(t[k]):.2f}, {max(t[k]):.2f}]  x{med / base:.3f}", flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--codecs", default="rgroup,rgroup_rot")
@@ -45,6 +81,8 @@ def main():
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--repeats", type=int, default=9)
     ap.add_argument("--json-out", default="", help="also write the results there as JSON")
+    ap.add_argument("--fork-variants", default="", help="e.g. 10,40: time fake_quant_fork against that many "
+                                                        "fake_quant calls + torch.cat instead of pack / unpack")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("codec_bench needs a GPU")
@@ -56,7 +94,9 @@ def main():
     imp = torch.rand(B, S, generator=g, device="cuda")
     out = {"shape": [B, S, H], "iters": a.iters, "repeats": a.repeats, "plan_bits": a.plan_bits,
            "device": torch.cuda.get_device_name(0), "results": []}
-    for dtype in (torch.float32, torch.bfloat16):
+    if a.fork_variants:
+        fork_bench(a, names, x32, out)
+    for dtype in () if a.fork_variants else (torch.float32, torch.bfloat16):
         x = x32.to(dtype)
         runs = {}
         for n in names:

@@ -34,6 +34,9 @@ def main():
                     help="fp32 = the reference's precision (h3 GEMMs); bf16 = the bf16 mode")
     ap.add_argument("--weight-values", default="bf16", choices=["bf16", "fp32"],
                     help="random weight values: bf16 as the HF checkpoint the reference upcasts, or full fp32")
+    ap.add_argument("--fork", action="store_true",
+                    help="fake-quantize each boundary layer's variants in one codec.fake_quant_fork pass "
+                         "(SweepConfig.fork) instead of one fake_quant per variant")
     a = ap.parse_args()
     dev = "cuda" if torch.cuda.is_available() else "cpu"
     dtype = torch.bfloat16 if (dev == "cuda" and a.dtype == "bf16") else torch.float32
@@ -43,7 +46,7 @@ def main():
     layers = [22, 18, 3, 23, 11] if cfg.num_layers == 24 else [1, 2]
     hw = torch.full((cfg.num_layers, cfg.num_heads), 1.0 / cfg.num_heads)
     sc = SweepConfig(["regular_importance", "weighted_importance", "last_row", "aggregate_till"], layers,
-                     [0, 0.25, 0.5, 0.75, 1], codec="ref_int4_global", head_weights=hw)
+                     [0, 0.25, 0.5, 0.75, 1], codec="ref_int4_global", head_weights=hw, fork=a.fork)
     toks = synthetic_stream(299_078, cfg.vocab_size, 0)
     wins = [w for w in sliding_windows(toks.shape[1], 512, 32) if w.length == 512][1:]
     bl = [b.to(dev) for b in batches(toks, wins[: (a.windows + a.warmup_batches * a.batch)], a.batch)]
@@ -64,7 +67,7 @@ def main():
            "windows": n, "seconds": dt, "windows_per_s": n / dt, "s_per_window": dt / n,
            "speedup_vs_T4_reference": T4_SECONDS_PER_WINDOW / (dt / n),
            "forward_tokens_per_s": eng.forward_tokens / dt, "dtype": str(dtype), "weights": prov,
-           "data": "synthetic", "batch": a.batch}
+           "data": "synthetic", "batch": a.batch, "fork": a.fork}
     print(json.dumps(out))
     if a.json_out:
         with open(a.json_out, "w") as f:
