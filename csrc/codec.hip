@@ -19,7 +19,7 @@
 #include "common.h"
 
 enum { FMT_BF16 = 0, FMT_INT8 = 1, FMT_INT4 = 2, FMT_INT2 = 3, FMT_F32 = 4, FMT_MXFP4 = 5, FMT_MXFP8 = 6, FMT_GRP = 7,
-       FMT_GRPR = 8, FMT_F16 = 9, FMT_F16S = 10 };
+       FMT_GRPR = 8, FMT_F16 = 9, FMT_F16S = 10, FMT_MXFP6 = 11, FMT_MXBF6 = 12 };
 // 16-bit wire formats of the rows a codec keeps in the activation dtype (codec/wire.py with_native_wire: the NATIVE
 // class of a codec resolves to one of them instead of the activation dtype, so fp32 activations cross at 2 B per
 // element).  FMT_BF16 (above): round to nearest even.  FMT_F16: IEEE binary16, the fp32 value converted with round to
@@ -59,6 +59,24 @@ enum { FMT_BF16 = 0, FMT_INT8 = 1, FMT_INT4 = 2, FMT_INT2 = 3, FMT_F32 = 4, FMT_
 // E8M0 scale 2^(floor(log2 max|x|) - emax) (emax 2 / 8), stored after the row's codes: [codes][H/32 scale bytes].
 // Quantize / dequantize with gfx950's scaled converts (v_cvt_scalef32_pk_fp4_f32 / _fp8_f32 and the inverses:
 // round-to-nearest-even of x / scale, saturating).
+// MXFP6 rows (FMT_MXFP6: E2M3 codes, bias 1, max 7.5, emax 2; FMT_MXBF6: E3M2 codes, bias 3, max 28, emax 4; no Inf /
+// NaN codes, subnormals kept; codec/wire.py with_mx_elem resolves a codec's FMT_MXFP4 classes to one of them): the MX
+// row layout [codes][H/32 E8M0 bytes] with a block's 32 six-bit codes as one little-endian bit stream of 24 bytes, code
+// c at bits [6 c, 6 c + 6), sign in the code's top bit; 25 H / 32 bytes a row (4-byte aligned when H % 128 == 0, as
+// at H = 896: 700 bytes), and every access to a row is 4 bytes wide (or one byte, for the scales).  Scale byte:
+// mx_scale_byte, as for the other MX rows.
+// Code: round to nearest even of clamp(x / X, +-max) on the element grid - the clamp first (x / X reaches (7.5, 8) /
+// (28, 32)), in software: nothing depends on whether the convert saturates.  gfx950's fp6 converts take a whole block
+// per lane (v_cvt_scalef32_2xpk16_{fp6,bf6}_f32: 2 x 16 floats -> 6 dwords; v_cvt_scalef32_pk32_f32_{fp6,bf6} back), so
+// these rows have their own data movement (mx6_pack_row / mx6_unpack_row: the row goes through the wave's LDS slice
+// from the 8-channels-per-lane layout of every other format to one block per lane).  The encode's result interleaves
+// its operands - code 2 p is operand 0's element p, code 2 p + 1 operand 1's (measured: tools/probes/mx6probe.hip; the
+// HIP headers' fallback concatenates them instead) - so operand 0 gets the block's even channels and operand 1 the odd
+// ones and the six dwords are the wire's stream; the decode returns element c from bits [6 c, 6 c + 6).  Messages with
+// such rows run the MX6 instantiations of pack_kernel / unpack_kernel (every 6-bit branch under `if constexpr (MX6)`;
+// they handle every other format but FMT_GRPR, FMT_F16 and FMT_F16S, which run_codec rejects next to 6-bit rows), so
+// the instantiations every other codec runs keep their instruction stream and allocate no LDS.  Header word 7 of such
+// a message is hi_fmt | lo_fmt << 8; unpack_kernel<MX6> decodes every row of a message that says otherwise to NaN.
 enum { SC_TOKEN = 0, SC_WINDOW = 1, SC_CHANNEL = 2, SC_NONE = 3 };
 enum { CH_MAXABS = 0, CH_MEAN = 1 };
 
@@ -72,28 +90,32 @@ struct CodecArgs {
   int grp_code_bytes;           // FMT_GRP / FMT_GRPR: sum over groups of 8 b_g (row = codes + 4 G scale bytes)
 };
 
-template <bool W16>
+template <bool W16, bool MX6>
 __device__ __forceinline__ int fmt_row_bytes(int fmt, int H) {
   if constexpr (W16) {
     if (fmt == FMT_F16) return 2 * H;
     if (fmt == FMT_F16S) return 2 * H + 4;
   }
+  if constexpr (MX6) {
+    if (fmt == FMT_MXFP6 || fmt == FMT_MXBF6) return 25 * (H / 32);
+  }
   return fmt == FMT_F32 ? 4 * H : fmt == FMT_BF16 ? 2 * H : fmt == FMT_INT8 ? H : fmt == FMT_INT4 ? H / 2 :
          fmt == FMT_MXFP4 ? H / 2 + H / 32 : fmt == FMT_MXFP8 ? H + H / 32 : H / 4;
 }
-template <bool ROT, bool W16>
+template <bool ROT, bool W16, bool MX6>
 __device__ __forceinline__ int row_bytes(const CodecArgs& a, int fmt) {
   if constexpr (ROT) {
     if (fmt == FMT_GRPR) return a.grp_code_bytes + 4 * (a.H / 64);
   }
-  return fmt == FMT_GRP ? a.grp_code_bytes + 4 * (a.H / 64) : fmt_row_bytes<W16>(fmt, a.H);
+  return fmt == FMT_GRP ? a.grp_code_bytes + 4 * (a.H / 64) : fmt_row_bytes<W16, MX6>(fmt, a.H);
 }
 // Formats whose rows carry their own scales (or none): no entry in the message's scale section.  A macro, and the
 // rotated format joined with `|`: the compiler simplifies the body of an inlined function on its own first, and the
 // rotated pack instantiations then allocate 66 / 82 instead of 56 / 74 VGPRs (NCH 2 / 4: a wave per SIMD less).
-#define SELF_SCALED(ROT, W16, fmt) \
+#define SELF_SCALED(ROT, W16, MX6, fmt) \
   (((fmt) == FMT_BF16 || (fmt) == FMT_F32 || (fmt) == FMT_MXFP4 || (fmt) == FMT_MXFP8 || (fmt) == FMT_GRP) | \
-   ((ROT) && (fmt) == FMT_GRPR) | ((W16) && ((fmt) == FMT_F16 || (fmt) == FMT_F16S)))
+   ((ROT) && (fmt) == FMT_GRPR) | ((W16) && ((fmt) == FMT_F16 || (fmt) == FMT_F16S)) | \
+   ((MX6) && ((fmt) == FMT_MXFP6 || (fmt) == FMT_MXBF6)))
 
 // Max-abs reductions of the codec propagate NaN (a unit holding a NaN / Inf must decode non-finite, and fmaxf drops a
 // NaN operand): they run on the bit pattern of |x| as an unsigned integer.  For non-negative floats the integer order
@@ -254,19 +276,19 @@ __device__ __forceinline__ void kvar_prefix(const CodecArgs& a, int b, int& Kb, 
 // among the class's rows of its window (lo_prefix), the class's rows of the windows before (b k / b (S - k) for fixed
 // k, the k vector's prefix sum for variable k, whose hi section starts right after the Sum k lo rows).
 struct RowSlot { uint8_t* p; int fmt, qmax, b; };
-template <bool ROT, bool W16>
+template <bool ROT, bool W16, bool MX6>
 __device__ __forceinline__ RowSlot row_slot(const CodecArgs& a, int row) {
   const int b = row / a.S, j = row - b * a.S;
   const uint32_t* mask = (const uint32_t*)(a.msg + a.off_mask) + (size_t)b * a.mw;
   bool is_lo;
   const int slot_lo = lo_prefix(mask, a.mw, j, is_lo);
   const int fmt = is_lo ? a.lo_fmt : a.hi_fmt;
-  const int rb = row_bytes<ROT, W16>(a, fmt);
+  const int rb = row_bytes<ROT, W16, MX6>(a, fmt);
   uint8_t* p;
   if (a.off_kvec >= 0) {
     int Kb, Kt;
     kvar_prefix(a, b, Kb, Kt);
-    const long long off_hi = a.off_lo + (((long long)Kt * row_bytes<ROT, W16>(a, a.lo_fmt) + 15) & ~15ll);
+    const long long off_hi = a.off_lo + (((long long)Kt * row_bytes<ROT, W16, MX6>(a, a.lo_fmt) + 15) & ~15ll);
     p = is_lo ? a.msg + a.off_lo + ((size_t)Kb + slot_lo) * rb
               : a.msg + off_hi + ((size_t)b * a.S - Kb + (j - slot_lo)) * rb;
   } else {
@@ -650,12 +672,92 @@ __device__ __forceinline__ F16Scale f16s_scale(uint32_t amb) {
   return {__uint_as_float((uint32_t)(127 + k) << 23), __uint_as_float((uint32_t)(127 - k) << 23)};
 }
 
-template <int NCH, class T, bool ROT = false, bool W16 = false>
+// ---- MXFP6 rows: one lane per 32-channel block -----------------------------------------------------------------------
+// A wave's LDS slice holds up to 4 chunks (512 channels each: the 8 channels of each of 64 lanes) of its row as fp32,
+// MX6_PASS(NCH) chunks per pass (NCH 8: two passes).  Logical float index of channel ch of a pass: ch, in 16-byte
+// slots s = ch / 4; block j = s / 8 owns slots 8 j .. 8 j + 7.  Two access patterns:
+//   chunk layout: lane l, chunk c: slots 128 c + 2 l and + 1 (its 8 channels; two b128 accesses);
+//   block layout: lane L = 16 c + j (chunk c's 16 blocks on lanes 16 c .. 16 c + 15): slots 8 L + i, i = 0 .. 7 (eight
+//                 b128 accesses: the block's 32 consecutive floats).
+// Bank model (64 banks of 4 bytes; a b128 access is served 16 lanes at a time, a lane covering the 4 banks of its slot,
+// slot mod 16): plain, the block layout puts lane L's access i on slot 8 L + i - mod 16 only L's parity varies, a 8-way
+// conflict within 16 lanes.  Swizzle: physical slot = s ^ ((j >> 1) & 7) with j = s >> 3 the slot's block - it permutes
+// the 8 slots of a block among themselves, so a block stays in its 128 bytes.
+//   block layout, access i: slot mod 16 = (i ^ ((L >> 1) & 7)) | (L & 1) << 3 - distinct for any 16 lanes with distinct
+//     L mod 16 (contiguous lanes, or the non-contiguous b128 groups {0-3, 12-15, 20-27}, ...): conflict-free.
+//   chunk layout, access e: j = 16 c + (l >> 2), so slot mod 16 = ((2 l + e) & 15) ^ ((l >> 3) & 7): lanes 8 m .. 8 m + 7
+//     cover the 8 slots of one parity (e ^ m's low bit) and lanes 8 (m + 1) .. the other parity: conflict-free for 16
+//     contiguous lanes and for the groups above.
+// Only the wave touches its slice, so no workgroup barrier: a wave's LDS instructions execute in issue order, and the
+// wavefront-scope fences (mx6_wave_sync) keep the compiler from moving one lane's reads above the stores of the others
+// or the next pass's stores above this pass's reads.  A row's format is wave-uniform, so every lane is there.
+constexpr int MX6_PASS(int nch) { return nch < 4 ? nch : 4; }
+typedef __attribute__((ext_vector_type(16))) float f32v16_t;
+typedef __attribute__((ext_vector_type(32))) float f32v32_t;
+typedef __attribute__((ext_vector_type(6))) uint32_t u32x6_t;
+// a row of 25 H / 32 bytes starts on a 4-byte boundary only when H % 128 == 0: its dword accesses are declared unaligned
+// (gfx950 serves them as dword accesses all the same)
+typedef uint32_t __attribute__((aligned(1))) u32_una_t;
+__device__ __forceinline__ void mx6_wave_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+__device__ __forceinline__ int mx6_chunk_slot(int c, int lane, int e) { return (128 * c + 2 * lane + e) ^ ((lane >> 3) & 7); }
+__device__ __forceinline__ int mx6_block_slot(int L, int i) { return (8 * L + i) ^ ((L >> 1) & 7); }
+
+template <int NCH>
+__device__ __forceinline__ void mx6_pack_row(uint8_t* __restrict__ row, int H, int fmt, const float (&v)[NCH][8],
+                                             float* __restrict__ slice) {
+  constexpr int P = MX6_PASS(NCH);
+  const int lane = threadIdx.x & 63, nblk = H / 32;
+  const bool e2m3 = fmt == FMT_MXFP6;
+#pragma unroll
+  for (int p0 = 0; p0 < NCH; p0 += P) {
+#pragma unroll
+    for (int c = 0; c < P; ++c) {
+      *(f32x4_t*)(slice + 4 * mx6_chunk_slot(c, lane, 0)) = f32x4_t{v[p0 + c][0], v[p0 + c][1], v[p0 + c][2], v[p0 + c][3]};
+      *(f32x4_t*)(slice + 4 * mx6_chunk_slot(c, lane, 1)) = f32x4_t{v[p0 + c][4], v[p0 + c][5], v[p0 + c][6], v[p0 + c][7]};
+    }
+    mx6_wave_sync();
+    const int blk = 16 * p0 + lane;          // the row's block on this lane
+    if (lane < 16 * P && blk < nblk) {
+      float x[32];
+#pragma unroll
+      for (int i = 0; i < 8; ++i) {
+        const f32x4_t t = *(const f32x4_t*)(slice + 4 * mx6_block_slot(lane, i));
+#pragma unroll
+        for (int e = 0; e < 4; ++e) x[4 * i + e] = t[e];
+      }
+      uint32_t amb = 0;
+#pragma unroll
+      for (int e = 0; e < 32; ++e) amb = umax(amb, abs_bits(x[e]));
+      const int sb = mx_scale_byte(__uint_as_float(amb), e2m3 ? 2 : 4);
+      const float X = e8m0_value(sb == MX_NAN ? 127 : sb);   // the codes of a NaN block are never read
+      const float lim = (e2m3 ? 7.5f : 28.f) * X;            // exact: a multiple of 2^-149 at X = 2^-127
+      f32v16_t ev, od;                                       // operand 0: codes 0, 2, ...; operand 1: codes 1, 3, ...
+#pragma unroll
+      for (int e = 0; e < 16; ++e) {
+        ev[e] = __builtin_amdgcn_fmed3f(x[2 * e], -lim, lim);       // one v_med3_f32; a NaN is in a NaN block only
+        od[e] = __builtin_amdgcn_fmed3f(x[2 * e + 1], -lim, lim);
+      }
+      const u32x6_t w = e2m3 ? __builtin_amdgcn_cvt_scalef32_2xpk16_fp6_f32(ev, od, X)
+                             : __builtin_amdgcn_cvt_scalef32_2xpk16_bf6_f32(ev, od, X);
+      u32_una_t* dst = (u32_una_t*)(row + 24 * blk);
+#pragma unroll
+      for (int i = 0; i < 6; ++i) dst[i] = w[i];
+      row[24 * nblk + blk] = (uint8_t)sb;
+    }
+    if (p0 + P < NCH) mx6_wave_sync();
+  }
+}
+
+template <int NCH, class T, bool ROT = false, bool W16 = false, bool MX6 = false>
 __global__ __launch_bounds__(256) void pack_kernel(CodecArgs a) {
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= a.B * a.S) return;
   const int lane = threadIdx.x & 63;
-  const RowSlot rs = row_slot<ROT, W16>(a, row);
+  const RowSlot rs = row_slot<ROT, W16, MX6>(a, row);
   uint8_t* dst = rs.p;
   const int fmt = rs.fmt, qmax = rs.qmax, b = rs.b;
   float v[NCH][8];
@@ -664,7 +766,7 @@ __global__ __launch_bounds__(256) void pack_kernel(CodecArgs a) {
 
   // scale / quantiser for this row
   float inv = 0.f, mul = 0.f;  // code = round(x * inv) for token & channel; window mode uses ref formula
-  const bool raw = SELF_SCALED(ROT, W16, fmt);
+  const bool raw = SELF_SCALED(ROT, W16, MX6, fmt);
   if (raw && a.scale_mode == SC_TOKEN && lane == 0) scales[row] = 0.f;
   if (!raw) {
     if (a.scale_mode == SC_TOKEN) {
@@ -679,6 +781,13 @@ __global__ __launch_bounds__(256) void pack_kernel(CodecArgs a) {
       inv = tok_inv(am, s);
     } else if (a.scale_mode == SC_WINDOW) {
       mul = scales[b];  // max|x| over the window's lo rows
+    }
+  }
+  if constexpr (MX6) {
+    __shared__ __attribute__((aligned(16))) float mx6_lds[4][MX6_PASS(NCH) * 512];
+    if (fmt == FMT_MXFP6 || fmt == FMT_MXBF6) {   // wave-uniform: the row's format
+      mx6_pack_row<NCH>(dst, a.H, fmt, v, mx6_lds[threadIdx.x >> 6]);
+      return;
     }
   }
   const float qmaxf = (float)qmax;
@@ -779,21 +888,79 @@ __device__ __forceinline__ void store8(float* dst, const float (&o)[8]) {
   *(f32x4_t*)(dst + 4) = f32x4_t{o[4], o[5], o[6], o[7]};
 }
 
-template <int NCH, class T, bool ROT = false, bool W16 = false>
+template <int NCH, class T>
+__device__ __forceinline__ void mx6_unpack_row(const uint8_t* __restrict__ row, int H, int fmt, T* __restrict__ out,
+                                               float* __restrict__ slice) {
+  constexpr int P = MX6_PASS(NCH);
+  const int lane = threadIdx.x & 63, nblk = H / 32;
+#pragma unroll
+  for (int p0 = 0; p0 < NCH; p0 += P) {
+    const int blk = 16 * p0 + lane;
+    if (lane < 16 * P && blk < nblk) {
+      const u32_una_t* src = (const u32_una_t*)(row + 24 * blk);
+      u32x6_t w;
+#pragma unroll
+      for (int i = 0; i < 6; ++i) w[i] = src[i];
+      const int sb = row[24 * nblk + blk];
+      const float X = e8m0_value(sb == MX_NAN ? 127 : sb);
+      f32v32_t x = fmt == FMT_MXFP6 ? __builtin_amdgcn_cvt_scalef32_pk32_f32_fp6(w, X)
+                                    : __builtin_amdgcn_cvt_scalef32_pk32_f32_bf6(w, X);
+#pragma unroll
+      for (int i = 0; i < 8; ++i) {
+        f32x4_t t;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) t[e] = sb == MX_NAN ? __builtin_nanf("") : x[4 * i + e];
+        *(f32x4_t*)(slice + 4 * mx6_block_slot(lane, i)) = t;
+      }
+    }
+    mx6_wave_sync();
+#pragma unroll
+    for (int c = 0; c < P; ++c) {
+      const int col = ((p0 + c) * 64 + lane) * 8;
+      if (col >= H) continue;
+      const f32x4_t t0 = *(const f32x4_t*)(slice + 4 * mx6_chunk_slot(c, lane, 0));
+      const f32x4_t t1 = *(const f32x4_t*)(slice + 4 * mx6_chunk_slot(c, lane, 1));
+      const float o[8] = {t0[0], t0[1], t0[2], t0[3], t1[0], t1[1], t1[2], t1[3]};
+      store8(out + col, o);
+    }
+    if (p0 + P < NCH) mx6_wave_sync();
+  }
+}
+
+template <int NCH, class T, bool ROT = false, bool W16 = false, bool MX6 = false>
 __global__ __launch_bounds__(256) void unpack_kernel(CodecArgs a) {
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= a.B * a.S) return;
   const int lane = threadIdx.x & 63;
-  const RowSlot rs = row_slot<ROT, W16>(a, row);
+  const RowSlot rs = row_slot<ROT, W16, MX6>(a, row);
   const uint8_t* src = rs.p;
   const int fmt = rs.fmt, qmax = rs.qmax, b = rs.b;
   const float* scales = (const float*)(a.msg + a.off_scale);
   float s = 0.f;
-  if (!SELF_SCALED(ROT, W16, fmt)) {
+  if (!SELF_SCALED(ROT, W16, MX6, fmt)) {
     if (a.scale_mode == SC_TOKEN) s = scales[row];
     else if (a.scale_mode == SC_WINDOW) s = scales[b];
   }
   T* out = (T*)a.x + (size_t)row * a.H;
+  if constexpr (MX6) {
+    __shared__ __attribute__((aligned(16))) float mx6_lds[4][MX6_PASS(NCH) * 512];
+    // header word 7 of a message with 6-bit rows names both classes' formats; one that disagrees with the formats this
+    // launch was given (encoded with another element type, or without the modifier) decodes to NaN - loud
+    if (((const int*)a.msg)[7] != (a.hi_fmt | a.lo_fmt << 8)) {
+      float o[8];
+      fill8(o, __builtin_nanf(""));
+#pragma unroll
+      for (int c = 0; c < NCH; ++c) {
+        const int col = (c * 64 + lane) * 8;
+        if (col < a.H) store8(out + col, o);
+      }
+      return;
+    }
+    if (fmt == FMT_MXFP6 || fmt == FMT_MXBF6) {   // wave-uniform: the row's format
+      mx6_unpack_row<NCH>(src, a.H, fmt, out, mx6_lds[threadIdx.x >> 6]);
+      return;
+    }
+  }
   float p16 = 1.f;   // FMT_F16S: the row's p (FMT_F16: 1, an exact multiply)
   if constexpr (W16) {
     if (fmt == FMT_F16S) p16 = *(const float*)(src + 2 * a.H);
@@ -1203,15 +1370,16 @@ EDGE_API int edge_rowmax(const float* in, float* out, int R, int H, hipStream_t 
 // A message with FMT_GRPR rows goes to the ROT instantiations (which handle every other format too).
 static bool has_fmt(int hi_fmt, int lo_fmt, int fmt) { return hi_fmt == fmt || lo_fmt == fmt; }
 
-template <bool PACK, int NCH, class T, bool ROT, bool W16 = false>
+template <bool PACK, int NCH, class T, bool ROT, bool W16 = false, bool MX6 = false>
 static void launch_codec(dim3 grid, hipStream_t st, const CodecArgs& a) {
-  if constexpr (PACK) hipLaunchKernelGGL((pack_kernel<NCH, T, ROT, W16>), grid, dim3(256), 0, st, a);
-  else hipLaunchKernelGGL((unpack_kernel<NCH, T, ROT, W16>), grid, dim3(256), 0, st, a);
+  if constexpr (PACK) hipLaunchKernelGGL((pack_kernel<NCH, T, ROT, W16, MX6>), grid, dim3(256), 0, st, a);
+  else hipLaunchKernelGGL((unpack_kernel<NCH, T, ROT, W16, MX6>), grid, dim3(256), 0, st, a);
 }
 
 // edge_pack / edge_unpack: argument checks, CodecArgs and the (ROT | W16 | plain) x activation dtype x NCH dispatch.
 // A message with FMT_F16 / FMT_F16S rows goes to the W16 instantiations (which handle every format but FMT_GRPR);
-// together with FMT_GRPR rows it is rejected before anything is launched.
+// together with FMT_GRPR rows it is rejected before anything is launched.  A message with FMT_MXFP6 / FMT_MXBF6 rows goes
+// to the MX6 instantiations; together with FMT_GRPR, FMT_F16 or FMT_F16S rows it is rejected the same way.
 template <bool PACK>
 static int run_codec(void* x, void* msg, long long om, long long os, long long oh, long long ol, long long okv,
                      long long opl, int B, int S, int H, int k, int hi_fmt, int lo_fmt, int scale_mode, int qmax_hi,
@@ -1219,7 +1387,8 @@ static int run_codec(void* x, void* msg, long long om, long long os, long long o
   if (H % 32) return (int)hipErrorInvalidValue;
   const bool rot = has_fmt(hi_fmt, lo_fmt, FMT_GRPR);
   const bool w16 = has_fmt(hi_fmt, lo_fmt, FMT_F16) || has_fmt(hi_fmt, lo_fmt, FMT_F16S);
-  if (rot && w16) return (int)hipErrorInvalidValue;
+  const bool mx6 = has_fmt(hi_fmt, lo_fmt, FMT_MXFP6) || has_fmt(hi_fmt, lo_fmt, FMT_MXBF6);
+  if ((rot && w16) || (mx6 && (rot || w16))) return (int)hipErrorInvalidValue;
   if ((rot || has_fmt(hi_fmt, lo_fmt, FMT_GRP)) && (H % 64 || opl < 0 || grp_code_bytes <= 0))
     return (int)hipErrorInvalidValue;
   CodecArgs a;
@@ -1236,6 +1405,8 @@ static int run_codec(void* x, void* msg, long long om, long long os, long long o
   else if (rot) DISPATCH_NCH(H, (launch_codec<PACK, NCH, bf16_t, true>(grid, st, a)));
   else if (w16 && x_f32) DISPATCH_NCH(H, (launch_codec<PACK, NCH, float, false, true>(grid, st, a)));
   else if (w16) DISPATCH_NCH(H, (launch_codec<PACK, NCH, bf16_t, false, true>(grid, st, a)));
+  else if (mx6 && x_f32) DISPATCH_NCH(H, (launch_codec<PACK, NCH, float, false, false, true>(grid, st, a)));
+  else if (mx6) DISPATCH_NCH(H, (launch_codec<PACK, NCH, bf16_t, false, false, true>(grid, st, a)));
   else if (x_f32) DISPATCH_NCH(H, (launch_codec<PACK, NCH, float, false>(grid, st, a)));
   else DISPATCH_NCH(H, (launch_codec<PACK, NCH, bf16_t, false>(grid, st, a)));
   return (int)hipGetLastError();

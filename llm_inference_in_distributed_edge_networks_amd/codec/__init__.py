@@ -26,6 +26,8 @@ mxfp4 / mxfp8          MXFP4 / MXFP8   --              E8M0 / 32ch  OCP microsca
                                                                     scaled converts)
 mixed_mxfp4_mxfp8      MXFP8 (E4M3)    MXFP4 (E2M1)    E8M0 / 32ch  configs 3-5 at microscaling widths
 mxfp4_keep             native dtype    MXFP4           E8M0 / 32ch  Q1 with MX blocks instead of one scale
+(the three above)      with_mx_elem "e2m3" / "e3m2": their MXFP4    MXFP6 rows, 6.25 bits per element
+                       rows as FP6 E2M3 / E3M2 codes                (gfx950 2xpk16 / pk32 fp6 converts)
 rgroup                 head groups     --              per group    every 64-channel group (one head) its
                                                                     own max-abs scale and 2/4/8-bit width
 mixed_rgroup_int8      int8            head groups     token/group  config 5 (relevance-allocated widths
@@ -51,6 +53,11 @@ The "native dtype" rows cross as fp32 (4 B per element) in the fp32 execution mo
 past 65504: loud) or fp16 with a per-row power-of-two scale (no finite row overflows, 8x below bf16's rounding error);
 see ``wire.py``.  BASELINE config 1 ("fp16 pass-through") is ``passthrough`` with ``"native_wire": "fp16"``.
 
+``with_mx_elem(spec, "e2m3" | "e3m2")`` (params key ``mx_elem``) fills the MX family's gap between 4.25 (``mxfp4``) and
+8.25 (``mxfp8``) bits per element: the codec's MXFP4 rows become MXFP6 rows - 32-channel E8M0 blocks of FP6 E2M3 (max
+7.5) or E3M2 (max 28) codes, 25 H / 32 bytes a row.  A modifier like ``with_native_wire``, not a new codec; not combined
+with a 16-bit native wire.
+
 ``fake_quant_fork(x, spec, B, S, variants, importances)`` is ``fake_quant`` for a whole list of (importance source, k)
 variants of one codec at once - the sweep's step between the shared prefix and the stacked suffix: one sort per
 source, one read of ``x``, one write per variant, bit-identical to the per-variant round trip (``fork_supported``: the
@@ -61,7 +68,7 @@ window (ascending importance, ties broken by position) are the lo class.
 """
 from . import plan  # noqa: F401  (codec.plan: the head-group bit plans)
 from .wire import (CODECS, CodecSpec, Layout, decode, encode, fake_quant, fake_quant_fork, fork_supported, get_codec,
-                   layout, message_bytes, select_mask, with_native_wire)
+                   layout, message_bytes, select_mask, with_mx_elem, with_native_wire)
 
 __all__ = ["CODECS", "CodecSpec", "Layout", "decode", "encode", "fake_quant", "fake_quant_fork", "fork_supported",
-           "get_codec", "layout", "message_bytes", "select_mask", "with_native_wire"]
+           "get_codec", "layout", "message_bytes", "select_mask", "with_mx_elem", "with_native_wire"]

@@ -37,6 +37,21 @@ sends them in a 16-bit row format instead; the header's hi-row-format word then 
   overflows, and ``|x' - x| <= max(2^-11 |x|, 2^(k - 25))``: 8x below bf16's rounding error.
 * ``"native"``: the activation dtype, as without the modifier.
 
+MXFP6 rows.  ``with_mx_elem(spec, name)`` - a modifier too - resolves every ``FMT_MXFP4`` class of a codec (``mxfp4``,
+``mixed_mxfp4_mxfp8``'s lo rows, ``mxfp4_keep``'s lo rows) to an OCP MX 6-bit element type at 6.25 bits per element,
+between mxfp4's 4.25 and mxfp8's 8.25:
+
+* ``"e2m3"`` (``FMT_MXFP6`` = 11): FP6 E2M3, bias 1, largest value 7.5, emax 2.
+* ``"e3m2"`` (``FMT_MXBF6`` = 12): FP6 E3M2, bias 3, largest value 28, emax 4.
+* ``"fp4"``: E2M1, as without the modifier.
+
+Neither 6-bit type has Inf / NaN codes, both have subnormals.  Row = ``[codes][H/32 E8M0 bytes]`` as for every MX row; a
+block's 32 six-bit codes are one little-endian bit stream of 24 bytes, code c at bits [6c, 6c + 6), sign in the code's
+top bit: 25 H / 32 bytes a row.  Code = round to nearest even of ``clamp(x / X, +-max)`` on the element grid (X the
+block's E8M0 scale; the clamp first: x / X reaches (7.5, 8) and (28, 32)).  With the modifier on, header word 7 is
+``hi_fmt | lo_fmt << 8``, and ``decode`` refuses a message whose formats are not its spec's.  Not combined with a 16-bit
+native wire, and such specs are not served by ``fake_quant_fork``.
+
 ``encode``/``decode`` run the gfx950 kernels of ``csrc/codec.hip`` for CUDA
 tensors and a bit-identical PyTorch implementation for CPU tensors.
 
@@ -59,13 +74,16 @@ MAGIC = 0x45444742
 VERSION = 1
 FMT_BF16, FMT_INT8, FMT_INT4, FMT_INT2, FMT_F32, FMT_MXFP4, FMT_MXFP8, FMT_GRP = 0, 1, 2, 3, 4, 5, 6, 7
 FMT_GRPR = 8                # FMT_GRP bytes whose codes and scales describe the Hadamard-rotated group
-MX_FORMATS = (FMT_MXFP4, FMT_MXFP8)
 FMT_F16, FMT_F16S = 9, 10   # 16-bit wires of NATIVE rows: IEEE binary16; binary16 codes + one fp32 power-of-two scale
+FMT_MXFP6, FMT_MXBF6 = 11, 12   # MX rows of FP6 E2M3 / E3M2 codes (with_mx_elem)
+MX6_FORMATS = (FMT_MXFP6, FMT_MXBF6)
+MX_FORMATS = (FMT_MXFP4, FMT_MXFP8) + MX6_FORMATS
 GRP_FORMATS = (FMT_GRP, FMT_GRPR)
 SC_TOKEN, SC_WINDOW, SC_CHANNEL, SC_NONE = 0, 1, 2, 3
 CH_MAXABS, CH_MEAN = 0, 1
 NATIVE = -1  # "keep in the activation dtype" (bf16 on GPU, fp32 in the CPU reference mode)
 NATIVE_WIRES = {"native": NATIVE, "bf16": FMT_BF16, "fp16": FMT_F16, "fp16s": FMT_F16S}   # with_native_wire
+MX_ELEMS = {"fp4": FMT_MXFP4, "e2m3": FMT_MXFP6, "e3m2": FMT_MXBF6}                         # with_mx_elem
 
 
 @dataclass(frozen=True)
@@ -82,6 +100,7 @@ class CodecSpec:
     needs_importance: bool = True
     plan: tuple | None = None    # FMT_GRP / FMT_GRPR rows: bits (GROUP_BITS) of every 64-channel group (with_plan)
     native_wire: int = NATIVE    # row format of the NATIVE classes on the wire (with_native_wire); NATIVE: the dtype's
+    mx_elem: int = FMT_MXFP4     # row format of the FMT_MXFP4 classes on the wire (with_mx_elem)
 
 
 CODECS = {c.name: c for c in [
@@ -147,7 +166,24 @@ def with_native_wire(spec: CodecSpec, name: str) -> CodecSpec:
     if name != "native" and not has_native_rows(spec):
         raise ValueError(f"codec {spec.name} keeps no rows in the activation dtype: native_wire {name!r} has nothing "
                          "to apply to")
+    if name != "native" and spec.mx_elem != FMT_MXFP4:
+        raise ValueError(f"native_wire {name!r} is not combined with 6-bit MX rows (mx_elem)")
     return spec if spec.native_wire == NATIVE_WIRES[name] else replace(spec, native_wire=NATIVE_WIRES[name])
+
+
+def with_mx_elem(spec: CodecSpec, name: str) -> CodecSpec:
+    """The codec with its FMT_MXFP4 rows sent with element type ``name``: "fp4" (E2M1, the spec itself) | "e2m3" |
+    "e3m2" (MXFP6 rows, module docstring).  A codec without FMT_MXFP4 rows takes "fp4" only; a 6-bit element type is
+    not combined with a 16-bit native wire."""
+    from dataclasses import replace
+    if name not in MX_ELEMS:
+        raise ValueError(f"mx_elem must be one of {tuple(MX_ELEMS)}, got {name!r}")
+    if name != "fp4":
+        if FMT_MXFP4 not in (spec.hi_fmt, spec.lo_fmt):
+            raise ValueError(f"codec {spec.name} has no MXFP4 rows: mx_elem {name!r} has nothing to apply to")
+        if spec.native_wire != NATIVE:
+            raise ValueError(f"mx_elem {name!r} is not combined with a 16-bit native wire (native_wire)")
+    return spec if spec.mx_elem == MX_ELEMS[name] else replace(spec, mx_elem=MX_ELEMS[name])
 
 
 def get_codec(name: str) -> CodecSpec:
@@ -220,14 +256,18 @@ def num_lo(spec: CodecSpec, ratio: float, S: int) -> int:
     return max(0, min(S, int(ratio * S)))
 
 
+def _resolve(fmt: int, spec: CodecSpec, native: int) -> int:
+    """A class's row format on the wire: the spec's, with its modifiers (native wire, MX element type) applied."""
+    return native if fmt == NATIVE else spec.mx_elem if fmt == FMT_MXFP4 else fmt
+
+
 @lru_cache(maxsize=256)
 def layout(spec: CodecSpec, B: int, S: int, H: int, k: int, dtype: torch.dtype = torch.bfloat16,
            kvar: bool = False) -> Layout:
     if H % 32:
         raise ValueError("hidden size must be a multiple of 32 for the packed formats")
     nf = native_fmt(dtype) if spec.native_wire == NATIVE else spec.native_wire
-    hi = nf if spec.hi_fmt == NATIVE else spec.hi_fmt
-    lo = nf if spec.lo_fmt == NATIVE else spec.lo_fmt
+    hi, lo = _resolve(spec.hi_fmt, spec, nf), _resolve(spec.lo_fmt, spec, nf)
     plan = None
     if hi in GRP_FORMATS or lo in GRP_FORMATS:
         if H % GROUP:
@@ -388,6 +428,39 @@ def _fp4_codes(v: torch.Tensor) -> torch.Tensor:
     return c | torch.signbit(v).to(torch.int64) << 3
 
 
+def _minifloat_grid(ebits: int, mbits: int, bias: int) -> torch.Tensor:
+    """The 2^(ebits + mbits) non-negative values of a sign / exponent / mantissa format without Inf / NaN codes, by code:
+    mantissa m of exponent field 0 is the subnormal m 2^(1 - bias - mbits), of field e > 0 (2^mbits + m) 2^(e - bias -
+    mbits).  All exact in fp32."""
+    c = torch.arange(1 << (ebits + mbits))
+    e, m = c >> mbits, c & ((1 << mbits) - 1)
+    return torch.where(e == 0, m, m + (1 << mbits)).float() * torch.exp2((e.clamp(min=1) - bias - mbits).float())
+
+
+@dataclass(frozen=True)
+class _Fp6:
+    """One FP6 element type: its grid (32 values by code), the midpoints of neighbours, the 64 values by signed code."""
+    grid: torch.Tensor
+    mids: torch.Tensor
+    values: torch.Tensor
+    emax: int
+
+
+def _fp6(ebits, mbits, bias) -> _Fp6:
+    g = _minifloat_grid(ebits, mbits, bias)
+    return _Fp6(g, (g[:-1] + g[1:]) * 0.5, torch.cat([g, -g]), int(math.log2(float(g[-1]))))
+
+
+def _fp6_codes(v: torch.Tensor, f: _Fp6) -> torch.Tensor:
+    """FP6 codes of v (clamped to the largest value, round to nearest, ties to the even code), sign in bit 5 - kept on
+    values that round to zero, as by the gfx950 scaled convert.  _fp4_codes' comparisons against the grid's
+    midpoints, from a table: a value on midpoint j has j midpoints below it and j + 1 at or below - the even one of
+    the two is its code; off a midpoint the two counts agree."""
+    a = v.abs().clamp(max=float(f.grid[-1])).contiguous()
+    below, upto = torch.bucketize(a, f.mids), torch.bucketize(a, f.mids, right=True)
+    return torch.where(below % 2 == 0, below, upto) | torch.signbit(v).to(torch.int64) << 5
+
+
 MX_NAN = 255                # E8M0 byte of a block that held a NaN / Inf (OCP: NaN): all 32 channels decode to NaN
 
 
@@ -404,16 +477,24 @@ def _e8m0(sb: torch.Tensor) -> torch.Tensor:
     return torch.where(sb == 0, torch.full_like(v, 2.0 ** -127), v)
 
 
+_FP6 = {FMT_MXFP6: _fp6(2, 3, 1), FMT_MXBF6: _fp6(3, 2, 3)}      # E2M3: max 7.5, emax 2; E3M2: max 28, emax 4
+_MX_EMAX = {FMT_MXFP4: 2, FMT_MXFP8: 8, FMT_MXFP6: _FP6[FMT_MXFP6].emax, FMT_MXBF6: _FP6[FMT_MXBF6].emax}
+
+
 def _mx_pack(rows: torch.Tensor, fmt: int) -> torch.Tensor:
     n, H = rows.shape
     blk = rows.float().reshape(n, H // 32, 32)
     am = blk.abs().amax(-1)                                                  # NaN if the block holds one
-    sb = _mx_exp(am, 2 if fmt == FMT_MXFP4 else 8)                           # [n, H/32]
+    sb = _mx_exp(am, _MX_EMAX[fmt])                                          # [n, H/32]
     y = blk / _e8m0(sb)[..., None]
     sb = torch.where(torch.isfinite(am), sb, torch.full_like(sb, MX_NAN))    # codes of such a block: don't care
     if fmt == FMT_MXFP4:
         c = _fp4_codes(y).reshape(n, H // 2, 2)
         codes = (c[..., 0] | (c[..., 1] << 4)).to(torch.uint8)
+    elif fmt in MX6_FORMATS:   # 4 codes = 3 bytes of the block's little-endian 6-bit stream
+        c = _fp6_codes(y, _FP6[fmt]).reshape(n, H // 4, 4)
+        w = c[..., 0] | (c[..., 1] << 6) | (c[..., 2] << 12) | (c[..., 3] << 18)
+        codes = torch.stack([w & 255, (w >> 8) & 255, w >> 16], -1).to(torch.uint8)
     else:
         codes = y.clamp(-448.0, 448.0).to(torch.float8_e4m3fn).view(torch.uint8).reshape(n, H)
     return torch.cat([codes.reshape(n, -1), sb.to(torch.uint8)], 1).reshape(-1)
@@ -421,11 +502,15 @@ def _mx_pack(rows: torch.Tensor, fmt: int) -> torch.Tensor:
 
 def _mx_unpack(b: torch.Tensor, fmt: int, n: int, H: int) -> torch.Tensor:
     r = b.reshape(n, -1)
-    nc = H // 2 if fmt == FMT_MXFP4 else H
+    nc = H // 2 if fmt == FMT_MXFP4 else 3 * H // 4 if fmt in MX6_FORMATS else H
     codes, sb = r[:, :nc], r[:, nc:].to(torch.int64)
     if fmt == FMT_MXFP4:
         c = torch.stack([codes & 15, codes >> 4], -1).reshape(n, H).to(torch.int64)
         v = _FP4_GRID[c & 7] * torch.where(c >= 8, -1.0, 1.0)
+    elif fmt in MX6_FORMATS:
+        b3 = codes.to(torch.int64).reshape(n, H // 4, 3)
+        w = b3[..., 0] | (b3[..., 1] << 8) | (b3[..., 2] << 16)
+        v = _FP6[fmt].values[torch.stack([(w >> (6 * e)) & 63 for e in range(4)], -1).reshape(n, H)]
     else:
         v = codes.contiguous().view(torch.float8_e4m3fn).float()
     out = v.reshape(n, H // 32, 32) * _e8m0(sb)[..., None]
@@ -580,8 +665,8 @@ def _int_rows(fmt: int, per_byte: int) -> RowFormat:
     return RowFormat(lambda H, plan: H // per_byte, False, pack, unpack)
 
 
-def _mx_rows(fmt: int, per_byte: int) -> RowFormat:    # codes, then one E8M0 byte per 32 channels
-    return RowFormat(lambda H, plan: H // per_byte + H // 32, True,
+def _mx_rows(fmt: int, code_bits: int) -> RowFormat:    # codes, then one E8M0 byte per 32 channels
+    return RowFormat(lambda H, plan: H * code_bits // 8 + H // 32, True,
                      lambda rows, c: _mx_pack(rows, fmt), lambda raw, n, c: _mx_unpack(raw, fmt, n, c.H))
 
 
@@ -597,7 +682,8 @@ ROW_FORMATS = {
     FMT_F32: RowFormat(lambda H, plan: 4 * H, True, lambda rows, c: _bytes(rows),
                        lambda raw, n, c: raw.view(torch.float32).reshape(n, c.H)),
     FMT_INT8: _int_rows(FMT_INT8, 1), FMT_INT4: _int_rows(FMT_INT4, 2), FMT_INT2: _int_rows(FMT_INT2, 4),
-    FMT_MXFP4: _mx_rows(FMT_MXFP4, 2), FMT_MXFP8: _mx_rows(FMT_MXFP8, 1),
+    FMT_MXFP4: _mx_rows(FMT_MXFP4, 4), FMT_MXFP8: _mx_rows(FMT_MXFP8, 8),
+    FMT_MXFP6: _mx_rows(FMT_MXFP6, 6), FMT_MXBF6: _mx_rows(FMT_MXBF6, 6),
     FMT_GRP: _grp_rows(False), FMT_GRPR: _grp_rows(True),
     FMT_F16: RowFormat(lambda H, plan: 2 * H, True, lambda rows, c: _bytes(rows.to(torch.float16)),
                        lambda raw, n, c: raw.view(torch.float16).reshape(n, c.H).float()),
@@ -606,8 +692,28 @@ ROW_FORMATS = {
 }
 
 
+def _fmt_word(spec: CodecSpec, L: Layout) -> int:
+    """Header word 7: the hi-row format; with 6-bit MX rows (with_mx_elem) the lo-row format too, in bits 8-15."""
+    return L.hi_fmt | L.lo_fmt << 8 if spec.mx_elem != FMT_MXFP4 else L.hi_fmt
+
+
 def _header(spec: CodecSpec, L: Layout) -> torch.Tensor:
-    return torch.tensor([MAGIC, VERSION, spec.cid, L.B, L.S, L.H, -1 if L.kvar else L.k, L.hi_fmt], dtype=torch.int32)
+    return torch.tensor([MAGIC, VERSION, spec.cid, L.B, L.S, L.H, -1 if L.kvar else L.k, _fmt_word(spec, L)],
+                        dtype=torch.int32)
+
+
+def _check_formats(spec: CodecSpec, L: Layout, msg: torch.Tensor | None = None) -> None:
+    """decode's refusal of a message whose row formats are not the spec's: the layout's against the spec with its
+    modifiers (any device, no read of the message), and the header's format word of a CPU message against the
+    layout's.  (The GPU kernels check the word of a message with 6-bit MX rows themselves and decode it to NaN.)"""
+    for name, got, fmt in (("hi", L.hi_fmt, spec.hi_fmt), ("lo", L.lo_fmt, spec.lo_fmt)):
+        want = (got if spec.native_wire == NATIVE and got in (FMT_BF16, FMT_F32) else spec.native_wire) \
+            if fmt == NATIVE else _resolve(fmt, spec, NATIVE)
+        if got != want:
+            raise ValueError(f"codec {spec.name}: the message's {name} rows have format {got}, the spec's {want}")
+    if msg is not None and int(msg[28:32].view(torch.int32)) != _fmt_word(spec, L):
+        raise ValueError(f"codec {spec.name}: header format word {int(msg[28:32].view(torch.int32))}, "
+                         f"the spec's {_fmt_word(spec, L)}")
 
 
 def _classes(spec, L, lo_mask, scales, msg_plan):
@@ -781,6 +887,7 @@ def encode(x: torch.Tensor, spec: CodecSpec, B: int, S: int, ratio: float = 0.0,
 
 def decode(msg: torch.Tensor, spec: CodecSpec, L: Layout, dtype=torch.bfloat16, out=None) -> torch.Tensor:
     """Unpack and dequantize a boundary message into ``[B*S, H]`` activations."""
+    _check_formats(spec, L, None if msg.is_cuda else msg)
     if msg.is_cuda:
         if out is None:
             out = torch.empty(L.B * L.S, L.H, dtype=dtype, device=msg.device)
@@ -822,7 +929,7 @@ def fork_supported(spec: CodecSpec, selection: str = "ratio") -> bool:
     fixed k, NATIVE rows in the activation dtype (the codecs the sweeps run: ref_int4_global, int4_token, int8_token,
     int8_token_keep, mixed_int4_int8, mixed_int2_int8).  Everything else keeps the per-variant ``fake_quant``."""
     uses_kvar(spec, selection)       # an unknown selection: ValueError
-    return (selection == "ratio" and spec.native_wire == NATIVE
+    return (selection == "ratio" and spec.native_wire == NATIVE and spec.mx_elem == FMT_MXFP4
             and spec.scale_mode in (SC_TOKEN, SC_WINDOW)
             and (spec.hi_fmt, spec.qmax_hi) in _FORK_ROWS and (spec.lo_fmt, spec.qmax_lo) in _FORK_ROWS)
 

@@ -50,6 +50,8 @@ class Params:
     native_wire: str = "native"              # rows a codec keeps in the activation dtype cross as: "native" (that dtype:
                                              # fp32 in the fp32 mode) | "bf16" | "fp16" | "fp16s" (codec/wire.py
                                              # with_native_wire); BASELINE config 1 literally: passthrough + "fp16"
+    mx_elem: str = "fp4"                     # element type of a codec's MXFP4 rows: "fp4" (E2M1) | "e2m3" | "e3m2" (MXFP6
+                                             # rows, 6.25 bits per element; codec/wire.py with_mx_elem)
     sweep_fork: bool = False                 # sweeps: all (method, ratio) variants of a boundary layer from one
                                              # codec.fake_quant_fork pass (bit-identical to the per-variant path)
     lrp_engine: str = "auto"                 # relevance pass: "auto" (HIP engine on a GPU, autograd on the CPU) |
@@ -107,6 +109,10 @@ class Params:
             from .codec import wire   # a wire no codec knows, or one for a codec without native rows: ValueError
             spec = wire.CODECS.get(self.codec) or wire.CODECS["passthrough"]
             wire.with_native_wire(spec, self.native_wire)
+        if self.mx_elem != "fp4":
+            from .codec import wire   # an element type no codec knows, or one for a codec without MXFP4 rows: ValueError
+            spec = wire.CODECS.get(self.codec) or wire.CODECS["passthrough"]
+            wire.with_mx_elem(wire.with_native_wire(spec, self.native_wire), self.mx_elem)
 
 
 def resolve_device(p: Params) -> str:

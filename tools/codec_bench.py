@@ -3,7 +3,10 @@
     python tools/codec_bench.py --codecs rgroup,rgroup_rot --plan-bits 4 --json-out OUT/codec_bench.json
     python tools/codec_bench.py --codecs passthrough,passthrough@bf16,passthrough@fp16,passthrough@fp16s
 
-``name@wire`` is codec ``name`` with its activation-dtype rows on the 16-bit wire ``wire`` (``with_native_wire``).
+    python tools/codec_bench.py --codecs mxfp8,mxfp4@e2m3,mxfp4@e3m2,mxfp4
+
+``name@wire`` is codec ``name`` with its activation-dtype rows on the 16-bit wire ``wire`` (``with_native_wire``),
+``name@e2m3`` / ``name@e3m2`` with its MXFP4 rows as MXFP6 rows of that element type (``with_mx_elem``).
 
 Every codec packs the same activations ([B * S, H], randn with one massive channel) into its own preallocated
 message (the pack kernel alone: selection and statistics run once, before) and decodes it into a preallocated
@@ -100,7 +103,9 @@ def main():
         x = x32.to(dtype)
         runs = {}
         for n in names:
-            spec = C.with_native_wire(C.get_codec(n.split("@")[0]), (n.split("@") + ["native"])[1])
+            base, mod = (n.split("@") + ["native"])[:2]
+            spec = C.with_mx_elem(C.get_codec(base), mod) if mod in W.MX_ELEMS else \
+                C.with_native_wire(C.get_codec(base), mod)
             if C.wire.needs_plan(spec):
                 spec = C.wire.with_plan(spec, (a.plan_bits,) * (H // 64))
             L = C.layout(spec, B, S, H, C.wire.num_lo(spec, a.ratio, S), dtype)
