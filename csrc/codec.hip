@@ -19,7 +19,8 @@
 #include "common.h"
 
 enum { FMT_BF16 = 0, FMT_INT8 = 1, FMT_INT4 = 2, FMT_INT2 = 3, FMT_F32 = 4, FMT_MXFP4 = 5, FMT_MXFP8 = 6, FMT_GRP = 7,
-       FMT_GRPR = 8, FMT_F16 = 9, FMT_F16S = 10, FMT_MXFP6 = 11, FMT_MXBF6 = 12 };
+       FMT_GRPR = 8, FMT_F16 = 9, FMT_F16S = 10, FMT_MXFP6 = 11, FMT_MXBF6 = 12,
+       FMT_MXFP4R = 13, FMT_MXFP8R = 14, FMT_MXFP6R = 15, FMT_MXBF6R = 16 };
 // 16-bit wire formats of the rows a codec keeps in the activation dtype (codec/wire.py with_native_wire: the NATIVE
 // class of a codec resolves to one of them instead of the activation dtype, so fp32 activations cross at 2 B per
 // element).  FMT_BF16 (above): round to nearest even.  FMT_F16: IEEE binary16, the fp32 value converted with round to
@@ -77,6 +78,28 @@ enum { FMT_BF16 = 0, FMT_INT8 = 1, FMT_INT4 = 2, FMT_INT2 = 3, FMT_F32 = 4, FMT_
 // they handle every other format but FMT_GRPR, FMT_F16 and FMT_F16S, which run_codec rejects next to 6-bit rows), so
 // the instantiations every other codec runs keep their instruction stream and allocate no LDS.  Header word 7 of such
 // a message is hi_fmt | lo_fmt << 8; unpack_kernel<MX6> decodes every row of a message that says otherwise to NaN.
+// Rotated MX rows (FMT_MXFP4R / FMT_MXFP8R / FMT_MXFP6R / FMT_MXBF6R; codec/wire.py with_mx_rot resolves every MX class
+// of a codec to its twin): the bytes of the plain row, [codes][H/32 E8M0 bytes], but codes and scale byte describe
+// y = H32 x / 4 of the block, H32 the natural-order Sylvester matrix (y_i = sum_j (-1)^popcount(i & j) x_j): a loud
+// channel of a block is spread over its 32 channels, and E2M1 no longer flushes what lies below 1/12 of it.  Encode:
+// five fp32 butterfly stages (a, b) -> (a + b, a - b) at channel strides 1, 2, 4, 8, 16 in that order, the lower index
+// keeping the sum, then one multiply by 0.25f, then the plain row's quantizer on y (max-abs on bit patterns,
+// mx_scale_byte, software clamp, convert).  Decode: the plain row's values y' = X grid, the same five stages, one
+// multiply by 0.125f (H32 H32 = 32 I; 32 / (4 * 8) = 1).  No multiply precedes an add anywhere, so there is nothing for
+// fp contraction to fuse and the CPU oracle (codec/wire.py _wht32) agrees bit for bit; the decoder's sums are
+// multiples of the grid quantum bounded by 32 max (9 / 11 / 14 / 23 bits for E2M1 / E2M3 / E3M2 / E4M3): exact, only
+// the ends of the exponent range round.  A block holding a NaN / Inf rotates to non-finite y: byte 255, 32 NaNs.  So
+// does a finite block whose butterflies overflow (max-abs from about 2^123 up) - loud, never clipped.
+// Where the stages run: a 4- or 8-bit row keeps the 8-channels-per-lane layout, so a block is the 4 lanes of one quad -
+// strides 1, 2, 4 are wht8 on a lane's own values, strides 8 and 16 pair lanes ^1 and ^2 of the quad by DPP quad_perm
+// moves (wht_quad: 16 per lane and chunk, on the VALU's own operand path - a constant __shfl_xor compiles to
+// ds_bpermute_b32 through the LDS crossbar, what FMT_GRPR's wht_lanes pays for).  A 6-bit row has the whole block on
+// one lane after mx6_pack_row's transposition (before mx6_unpack_row's): all five stages are wht32 on its 32 values,
+// 80 add / sub, on the natural-order block - before the even / odd operand interleave of the convert.  Messages with
+// such rows run the MXR instantiations of pack_kernel / unpack_kernel (every rotated branch under `if constexpr
+// (MXR)`; MXR x MX6 when a class is 6-bit, the only ones of the MXR family with LDS), so the instantiations every
+// other codec runs keep their instruction stream.  Header word 7 is hi_fmt | lo_fmt << 8 as for 6-bit rows, and
+// unpack_kernel<MXR> decodes a message that says otherwise to NaN.  Not next to FMT_GRPR, FMT_F16, FMT_F16S rows.
 enum { SC_TOKEN = 0, SC_WINDOW = 1, SC_CHANNEL = 2, SC_NONE = 3 };
 enum { CH_MAXABS = 0, CH_MEAN = 1 };
 
@@ -90,7 +113,7 @@ struct CodecArgs {
   int grp_code_bytes;           // FMT_GRP / FMT_GRPR: sum over groups of 8 b_g (row = codes + 4 G scale bytes)
 };
 
-template <bool W16, bool MX6>
+template <bool W16, bool MX6, bool MXR = false>
 __device__ __forceinline__ int fmt_row_bytes(int fmt, int H) {
   if constexpr (W16) {
     if (fmt == FMT_F16) return 2 * H;
@@ -99,23 +122,31 @@ __device__ __forceinline__ int fmt_row_bytes(int fmt, int H) {
   if constexpr (MX6) {
     if (fmt == FMT_MXFP6 || fmt == FMT_MXBF6) return 25 * (H / 32);
   }
+  if constexpr (MXR) {   // a rotated row has the bytes of its plain twin
+    if (fmt == FMT_MXFP4R) return H / 2 + H / 32;
+    if (fmt == FMT_MXFP8R) return H + H / 32;
+    if constexpr (MX6) {
+      if (fmt == FMT_MXFP6R || fmt == FMT_MXBF6R) return 25 * (H / 32);
+    }
+  }
   return fmt == FMT_F32 ? 4 * H : fmt == FMT_BF16 ? 2 * H : fmt == FMT_INT8 ? H : fmt == FMT_INT4 ? H / 2 :
          fmt == FMT_MXFP4 ? H / 2 + H / 32 : fmt == FMT_MXFP8 ? H + H / 32 : H / 4;
 }
-template <bool ROT, bool W16, bool MX6>
+template <bool ROT, bool W16, bool MX6, bool MXR = false>
 __device__ __forceinline__ int row_bytes(const CodecArgs& a, int fmt) {
   if constexpr (ROT) {
     if (fmt == FMT_GRPR) return a.grp_code_bytes + 4 * (a.H / 64);
   }
-  return fmt == FMT_GRP ? a.grp_code_bytes + 4 * (a.H / 64) : fmt_row_bytes<W16, MX6>(fmt, a.H);
+  return fmt == FMT_GRP ? a.grp_code_bytes + 4 * (a.H / 64) : fmt_row_bytes<W16, MX6, MXR>(fmt, a.H);
 }
 // Formats whose rows carry their own scales (or none): no entry in the message's scale section.  A macro, and the
 // rotated format joined with `|`: the compiler simplifies the body of an inlined function on its own first, and the
 // rotated pack instantiations then allocate 66 / 82 instead of 56 / 74 VGPRs (NCH 2 / 4: a wave per SIMD less).
-#define SELF_SCALED(ROT, W16, MX6, fmt) \
+#define SELF_SCALED(ROT, W16, MX6, MXR, fmt) \
   (((fmt) == FMT_BF16 || (fmt) == FMT_F32 || (fmt) == FMT_MXFP4 || (fmt) == FMT_MXFP8 || (fmt) == FMT_GRP) | \
    ((ROT) && (fmt) == FMT_GRPR) | ((W16) && ((fmt) == FMT_F16 || (fmt) == FMT_F16S)) | \
-   ((MX6) && ((fmt) == FMT_MXFP6 || (fmt) == FMT_MXBF6)))
+   ((MX6) && ((fmt) == FMT_MXFP6 || (fmt) == FMT_MXBF6)) | \
+   ((MXR) && ((fmt) == FMT_MXFP4R || (fmt) == FMT_MXFP8R || (fmt) == FMT_MXFP6R || (fmt) == FMT_MXBF6R)))
 
 // Max-abs reductions of the codec propagate NaN (a unit holding a NaN / Inf must decode non-finite, and fmaxf drops a
 // NaN operand): they run on the bit pattern of |x| as an unsigned integer.  For non-negative floats the integer order
@@ -276,19 +307,19 @@ __device__ __forceinline__ void kvar_prefix(const CodecArgs& a, int b, int& Kb, 
 // among the class's rows of its window (lo_prefix), the class's rows of the windows before (b k / b (S - k) for fixed
 // k, the k vector's prefix sum for variable k, whose hi section starts right after the Sum k lo rows).
 struct RowSlot { uint8_t* p; int fmt, qmax, b; };
-template <bool ROT, bool W16, bool MX6>
+template <bool ROT, bool W16, bool MX6, bool MXR = false>
 __device__ __forceinline__ RowSlot row_slot(const CodecArgs& a, int row) {
   const int b = row / a.S, j = row - b * a.S;
   const uint32_t* mask = (const uint32_t*)(a.msg + a.off_mask) + (size_t)b * a.mw;
   bool is_lo;
   const int slot_lo = lo_prefix(mask, a.mw, j, is_lo);
   const int fmt = is_lo ? a.lo_fmt : a.hi_fmt;
-  const int rb = row_bytes<ROT, W16, MX6>(a, fmt);
+  const int rb = row_bytes<ROT, W16, MX6, MXR>(a, fmt);
   uint8_t* p;
   if (a.off_kvec >= 0) {
     int Kb, Kt;
     kvar_prefix(a, b, Kb, Kt);
-    const long long off_hi = a.off_lo + (((long long)Kt * row_bytes<ROT, W16, MX6>(a, a.lo_fmt) + 15) & ~15ll);
+    const long long off_hi = a.off_lo + (((long long)Kt * row_bytes<ROT, W16, MX6, MXR>(a, a.lo_fmt) + 15) & ~15ll);
     p = is_lo ? a.msg + a.off_lo + ((size_t)Kb + slot_lo) * rb
               : a.msg + off_hi + ((size_t)b * a.S - Kb + (j - slot_lo)) * rb;
   } else {
@@ -412,11 +443,27 @@ __device__ __forceinline__ int mx_scale_byte(float am, int emax) {
 }
 __device__ __forceinline__ float e8m0_value(int sb) { return sb ? __uint_as_float((uint32_t)sb << 23) : __uint_as_float(0x00400000u); }
 
+// A value of lane ^ 1 (QUAD_X1) or lane ^ 2 (QUAD_X2) of the lane's quad by one DPP quad_perm move: dpp_ctrl holds the
+// source lane of quad positions 0..3, two bits each ([1, 0, 3, 2] and [2, 3, 0, 1]).  Every lane of the quad must be
+// active (a disabled source lane yields the `old` operand, 0).
+enum { QUAD_X1 = 0xB1, QUAD_X2 = 0x4E };
+template <int CTRL>
+__device__ __forceinline__ uint32_t quad_mov(uint32_t x) {
+  return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, CTRL, 0xf, 0xf, false);
+}
+
+// QUAD (the rotated instantiations only): the block's max-abs over its 4 lanes by quad moves instead of shuffles.
+template <bool QUAD = false>
 __device__ __forceinline__ void mx_pack8(uint8_t* __restrict__ row, int H, int col, int fmt, const float (&v)[8]) {
   const int lane = threadIdx.x & 63;
   uint32_t amb = umax8(v);
-  amb = umax(amb, __shfl_xor(amb, 1, 64));
-  amb = umax(amb, __shfl_xor(amb, 2, 64));
+  if constexpr (QUAD) {
+    amb = umax(amb, quad_mov<QUAD_X1>(amb));
+    amb = umax(amb, quad_mov<QUAD_X2>(amb));
+  } else {
+    amb = umax(amb, __shfl_xor(amb, 1, 64));
+    amb = umax(amb, __shfl_xor(amb, 2, 64));
+  }
   const int sb = mx_scale_byte(__uint_as_float(amb), fmt == FMT_MXFP4 ? 2 : 8);
   const float X = e8m0_value(sb == MX_NAN ? 127 : sb);   // the codes of a NaN block are never read
   if (fmt == FMT_MXFP4) {
@@ -464,6 +511,46 @@ __device__ __forceinline__ void mx_unpack8(const uint8_t* __restrict__ row, int 
     put4(o, p0, p1, p2, p3);
   }
   if (sb == MX_NAN) fill8(o, __builtin_nanf(""));
+}
+
+// Rotated MX rows of 4- and 8-bit codes: the unnormalised 32-point Walsh-Hadamard transform of a block held 8
+// consecutive channels per lane by the 4 lanes of a quad (col = (64 c + lane) 8: block = lane >> 2 of its chunk).
+// Strides 1, 2, 4 are wht8 (below) on the lane's own values; strides 8 and 16 pair lanes ^1 and ^2 (wht_quad): the lane
+// with the bit clear holds a and keeps a + b, its partner holds b and keeps a - b = a + (-b) - the partner flips its
+// own sign bit and both add, 8 DPP moves, 8 xors and 8 adds a stride, no LDS.
+// Every lane of a quad must be at the moves: H % 32 == 0 makes the col >= H early-out drop whole quads, and a row's
+// format is wave-uniform (row_slot), so the lanes of a quad take the rotated branch together or not at all.
+template <class V>
+__device__ __forceinline__ void wht8(V (&v)[8]);
+__device__ __forceinline__ void wht_quad(float (&v)[8]) {
+  const uint32_t lane = threadIdx.x & 63;
+  const uint32_t s1 = (lane & 1u) << 31, s2 = (lane & 2u) << 30;
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    const uint32_t u = __float_as_uint(v[e]);
+    v[e] = __uint_as_float(quad_mov<QUAD_X1>(u)) + __uint_as_float(u ^ s1);
+  }
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    const uint32_t u = __float_as_uint(v[e]);
+    v[e] = __uint_as_float(quad_mov<QUAD_X2>(u)) + __uint_as_float(u ^ s2);
+  }
+}
+// fmt: the plain twin's (FMT_MXFP4 / FMT_MXFP8); the lane's values are rotated in place (their last use)
+__device__ __forceinline__ void mx_pack8_rot(uint8_t* __restrict__ row, int H, int col, int fmt, float (&y)[8]) {
+  wht8(y);
+  wht_quad(y);
+#pragma unroll
+  for (int e = 0; e < 8; ++e) y[e] *= 0.25f;
+  mx_pack8<true>(row, H, col, fmt, y);
+}
+// A NaN block (byte 255) leaves mx_unpack8 as 32 NaNs and the butterflies as 32 NaNs.
+__device__ __forceinline__ void mx_unpack8_rot(const uint8_t* __restrict__ row, int H, int col, int fmt, float (&o)[8]) {
+  mx_unpack8(row, H, col, fmt, o);
+  wht8(o);
+  wht_quad(o);
+#pragma unroll
+  for (int e = 0; e < 8; ++e) o[e] *= 0.125f;
 }
 
 // FMT_GRP: the 8 lanes holding channels [64 g, 64 g + 64) of a row (8 values each) quantize their group.
@@ -706,7 +793,24 @@ __device__ __forceinline__ void mx6_wave_sync() {
 __device__ __forceinline__ int mx6_chunk_slot(int c, int lane, int e) { return (128 * c + 2 * lane + e) ^ ((lane >> 3) & 7); }
 __device__ __forceinline__ int mx6_block_slot(int L, int i) { return (8 * L + i) ^ ((L >> 1) & 7); }
 
-template <int NCH>
+// Rotated 6-bit rows: the lane owns the block, so the five stages of the unnormalised 32-point Walsh-Hadamard transform
+// (strides 1, 2, 4, 8, 16, the lower index keeping the sum: 80 add / sub) run on its 32 values in place - X an array or
+// a vector of 32 floats, in natural channel order.
+template <class X>
+__device__ __forceinline__ void wht32(X& x) {
+#pragma unroll
+  for (int h = 1; h < 32; h <<= 1)
+#pragma unroll
+    for (int e = 0; e < 32; ++e)
+      if (!(e & h)) {
+        const float a = x[e], b = x[e + h];
+        x[e] = a + b;
+        x[e + h] = a - b;
+      }
+}
+
+// fmt: FMT_MXFP6 / FMT_MXBF6, the element type; R6: the row is the rotated twin's
+template <int NCH, bool R6 = false>
 __device__ __forceinline__ void mx6_pack_row(uint8_t* __restrict__ row, int H, int fmt, const float (&v)[NCH][8],
                                              float* __restrict__ slice) {
   constexpr int P = MX6_PASS(NCH);
@@ -728,6 +832,11 @@ __device__ __forceinline__ void mx6_pack_row(uint8_t* __restrict__ row, int H, i
         const f32x4_t t = *(const f32x4_t*)(slice + 4 * mx6_block_slot(lane, i));
 #pragma unroll
         for (int e = 0; e < 4; ++e) x[4 * i + e] = t[e];
+      }
+      if constexpr (R6) {   // y = H32 x / 4 of the natural-order block, before the even / odd split below
+        wht32(x);
+#pragma unroll
+        for (int e = 0; e < 32; ++e) x[e] *= 0.25f;
       }
       uint32_t amb = 0;
 #pragma unroll
@@ -752,12 +861,12 @@ __device__ __forceinline__ void mx6_pack_row(uint8_t* __restrict__ row, int H, i
   }
 }
 
-template <int NCH, class T, bool ROT = false, bool W16 = false, bool MX6 = false>
+template <int NCH, class T, bool ROT = false, bool W16 = false, bool MX6 = false, bool MXR = false>
 __global__ __launch_bounds__(256) void pack_kernel(CodecArgs a) {
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= a.B * a.S) return;
   const int lane = threadIdx.x & 63;
-  const RowSlot rs = row_slot<ROT, W16, MX6>(a, row);
+  const RowSlot rs = row_slot<ROT, W16, MX6, MXR>(a, row);
   uint8_t* dst = rs.p;
   const int fmt = rs.fmt, qmax = rs.qmax, b = rs.b;
   float v[NCH][8];
@@ -766,7 +875,7 @@ __global__ __launch_bounds__(256) void pack_kernel(CodecArgs a) {
 
   // scale / quantiser for this row
   float inv = 0.f, mul = 0.f;  // code = round(x * inv) for token & channel; window mode uses ref formula
-  const bool raw = SELF_SCALED(ROT, W16, MX6, fmt);
+  const bool raw = SELF_SCALED(ROT, W16, MX6, MXR, fmt);
   if (raw && a.scale_mode == SC_TOKEN && lane == 0) scales[row] = 0.f;
   if (!raw) {
     if (a.scale_mode == SC_TOKEN) {
@@ -788,6 +897,12 @@ __global__ __launch_bounds__(256) void pack_kernel(CodecArgs a) {
     if (fmt == FMT_MXFP6 || fmt == FMT_MXBF6) {   // wave-uniform: the row's format
       mx6_pack_row<NCH>(dst, a.H, fmt, v, mx6_lds[threadIdx.x >> 6]);
       return;
+    }
+    if constexpr (MXR) {
+      if (fmt == FMT_MXFP6R || fmt == FMT_MXBF6R) {
+        mx6_pack_row<NCH, true>(dst, a.H, fmt == FMT_MXFP6R ? FMT_MXFP6 : FMT_MXBF6, v, mx6_lds[threadIdx.x >> 6]);
+        return;
+      }
     }
   }
   const float qmaxf = (float)qmax;
@@ -816,6 +931,12 @@ __global__ __launch_bounds__(256) void pack_kernel(CodecArgs a) {
     if (fmt == FMT_MXFP4 || fmt == FMT_MXFP8) {
       mx_pack8(dst, a.H, col, fmt, v[c]);
       continue;
+    }
+    if constexpr (MXR) {   // all 4 lanes of the block's quad are here (wht_quad)
+      if (fmt == FMT_MXFP4R || fmt == FMT_MXFP8R) {
+        mx_pack8_rot(dst, a.H, col, fmt == FMT_MXFP4R ? FMT_MXFP4 : FMT_MXFP8, v[c]);
+        continue;
+      }
     }
     if (fmt == FMT_GRP) {
       grp_pack8(dst, a, col, v[c]);
@@ -888,7 +1009,7 @@ __device__ __forceinline__ void store8(float* dst, const float (&o)[8]) {
   *(f32x4_t*)(dst + 4) = f32x4_t{o[4], o[5], o[6], o[7]};
 }
 
-template <int NCH, class T>
+template <int NCH, class T, bool R6 = false>
 __device__ __forceinline__ void mx6_unpack_row(const uint8_t* __restrict__ row, int H, int fmt, T* __restrict__ out,
                                                float* __restrict__ slice) {
   constexpr int P = MX6_PASS(NCH);
@@ -905,6 +1026,11 @@ __device__ __forceinline__ void mx6_unpack_row(const uint8_t* __restrict__ row, 
       const float X = e8m0_value(sb == MX_NAN ? 127 : sb);
       f32v32_t x = fmt == FMT_MXFP6 ? __builtin_amdgcn_cvt_scalef32_pk32_f32_fp6(w, X)
                                     : __builtin_amdgcn_cvt_scalef32_pk32_f32_bf6(w, X);
+      if constexpr (R6) {   // x' = H32 y' / 8 (a NaN block's values are replaced below all the same)
+        wht32(x);
+#pragma unroll
+        for (int e = 0; e < 32; ++e) x[e] *= 0.125f;
+      }
 #pragma unroll
       for (int i = 0; i < 8; ++i) {
         f32x4_t t;
@@ -927,25 +1053,24 @@ __device__ __forceinline__ void mx6_unpack_row(const uint8_t* __restrict__ row, 
   }
 }
 
-template <int NCH, class T, bool ROT = false, bool W16 = false, bool MX6 = false>
+template <int NCH, class T, bool ROT = false, bool W16 = false, bool MX6 = false, bool MXR = false>
 __global__ __launch_bounds__(256) void unpack_kernel(CodecArgs a) {
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= a.B * a.S) return;
   const int lane = threadIdx.x & 63;
-  const RowSlot rs = row_slot<ROT, W16, MX6>(a, row);
+  const RowSlot rs = row_slot<ROT, W16, MX6, MXR>(a, row);
   const uint8_t* src = rs.p;
   const int fmt = rs.fmt, qmax = rs.qmax, b = rs.b;
   const float* scales = (const float*)(a.msg + a.off_scale);
   float s = 0.f;
-  if (!SELF_SCALED(ROT, W16, MX6, fmt)) {
+  if (!SELF_SCALED(ROT, W16, MX6, MXR, fmt)) {
     if (a.scale_mode == SC_TOKEN) s = scales[row];
     else if (a.scale_mode == SC_WINDOW) s = scales[b];
   }
   T* out = (T*)a.x + (size_t)row * a.H;
-  if constexpr (MX6) {
-    __shared__ __attribute__((aligned(16))) float mx6_lds[4][MX6_PASS(NCH) * 512];
-    // header word 7 of a message with 6-bit rows names both classes' formats; one that disagrees with the formats this
-    // launch was given (encoded with another element type, or without the modifier) decodes to NaN - loud
+  if constexpr (MX6 || MXR) {
+    // header word 7 of a message with 6-bit or rotated MX rows names both classes' formats; one that disagrees with the
+    // formats this launch was given (encoded with another element type, or without the modifier) decodes to NaN - loud
     if (((const int*)a.msg)[7] != (a.hi_fmt | a.lo_fmt << 8)) {
       float o[8];
       fill8(o, __builtin_nanf(""));
@@ -956,9 +1081,19 @@ __global__ __launch_bounds__(256) void unpack_kernel(CodecArgs a) {
       }
       return;
     }
+  }
+  if constexpr (MX6) {
+    __shared__ __attribute__((aligned(16))) float mx6_lds[4][MX6_PASS(NCH) * 512];
     if (fmt == FMT_MXFP6 || fmt == FMT_MXBF6) {   // wave-uniform: the row's format
       mx6_unpack_row<NCH>(src, a.H, fmt, out, mx6_lds[threadIdx.x >> 6]);
       return;
+    }
+    if constexpr (MXR) {
+      if (fmt == FMT_MXFP6R || fmt == FMT_MXBF6R) {
+        mx6_unpack_row<NCH, T, true>(src, a.H, fmt == FMT_MXFP6R ? FMT_MXFP6 : FMT_MXBF6, out,
+                                     mx6_lds[threadIdx.x >> 6]);
+        return;
+      }
     }
   }
   float p16 = 1.f;   // FMT_F16S: the row's p (FMT_F16: 1, an exact multiply)
@@ -996,6 +1131,14 @@ __global__ __launch_bounds__(256) void unpack_kernel(CodecArgs a) {
       mx_unpack8(src, a.H, col, fmt, o);
       store8(out + col, o);
       continue;
+    }
+    if constexpr (MXR) {   // all 4 lanes of the block's quad are here (wht_quad)
+      if (fmt == FMT_MXFP4R || fmt == FMT_MXFP8R) {
+        float o[8];
+        mx_unpack8_rot(src, a.H, col, fmt == FMT_MXFP4R ? FMT_MXFP4 : FMT_MXFP8, o);
+        store8(out + col, o);
+        continue;
+      }
     }
     if (fmt == FMT_GRP) {
       float o[8];
@@ -1370,16 +1513,17 @@ EDGE_API int edge_rowmax(const float* in, float* out, int R, int H, hipStream_t 
 // A message with FMT_GRPR rows goes to the ROT instantiations (which handle every other format too).
 static bool has_fmt(int hi_fmt, int lo_fmt, int fmt) { return hi_fmt == fmt || lo_fmt == fmt; }
 
-template <bool PACK, int NCH, class T, bool ROT, bool W16 = false, bool MX6 = false>
+template <bool PACK, int NCH, class T, bool ROT, bool W16 = false, bool MX6 = false, bool MXR = false>
 static void launch_codec(dim3 grid, hipStream_t st, const CodecArgs& a) {
-  if constexpr (PACK) hipLaunchKernelGGL((pack_kernel<NCH, T, ROT, W16, MX6>), grid, dim3(256), 0, st, a);
-  else hipLaunchKernelGGL((unpack_kernel<NCH, T, ROT, W16, MX6>), grid, dim3(256), 0, st, a);
+  if constexpr (PACK) hipLaunchKernelGGL((pack_kernel<NCH, T, ROT, W16, MX6, MXR>), grid, dim3(256), 0, st, a);
+  else hipLaunchKernelGGL((unpack_kernel<NCH, T, ROT, W16, MX6, MXR>), grid, dim3(256), 0, st, a);
 }
 
 // edge_pack / edge_unpack: argument checks, CodecArgs and the (ROT | W16 | plain) x activation dtype x NCH dispatch.
 // A message with FMT_F16 / FMT_F16S rows goes to the W16 instantiations (which handle every format but FMT_GRPR);
 // together with FMT_GRPR rows it is rejected before anything is launched.  A message with FMT_MXFP6 / FMT_MXBF6 rows goes
-// to the MX6 instantiations; together with FMT_GRPR, FMT_F16 or FMT_F16S rows it is rejected the same way.
+// to the MX6 instantiations; together with FMT_GRPR, FMT_F16 or FMT_F16S rows it is rejected the same way.  A message
+// with rotated MX rows goes to the MXR instantiations - MXR x MX6 when one of them is 6-bit - under the same rejections.
 template <bool PACK>
 static int run_codec(void* x, void* msg, long long om, long long os, long long oh, long long ol, long long okv,
                      long long opl, int B, int S, int H, int k, int hi_fmt, int lo_fmt, int scale_mode, int qmax_hi,
@@ -1387,8 +1531,10 @@ static int run_codec(void* x, void* msg, long long om, long long os, long long o
   if (H % 32) return (int)hipErrorInvalidValue;
   const bool rot = has_fmt(hi_fmt, lo_fmt, FMT_GRPR);
   const bool w16 = has_fmt(hi_fmt, lo_fmt, FMT_F16) || has_fmt(hi_fmt, lo_fmt, FMT_F16S);
-  const bool mx6 = has_fmt(hi_fmt, lo_fmt, FMT_MXFP6) || has_fmt(hi_fmt, lo_fmt, FMT_MXBF6);
-  if ((rot && w16) || (mx6 && (rot || w16))) return (int)hipErrorInvalidValue;
+  const bool mxr6 = has_fmt(hi_fmt, lo_fmt, FMT_MXFP6R) || has_fmt(hi_fmt, lo_fmt, FMT_MXBF6R);
+  const bool mxr = mxr6 || has_fmt(hi_fmt, lo_fmt, FMT_MXFP4R) || has_fmt(hi_fmt, lo_fmt, FMT_MXFP8R);
+  const bool mx6 = mxr6 || has_fmt(hi_fmt, lo_fmt, FMT_MXFP6) || has_fmt(hi_fmt, lo_fmt, FMT_MXBF6);
+  if ((rot && w16) || ((mx6 || mxr) && (rot || w16))) return (int)hipErrorInvalidValue;
   if ((rot || has_fmt(hi_fmt, lo_fmt, FMT_GRP)) && (H % 64 || opl < 0 || grp_code_bytes <= 0))
     return (int)hipErrorInvalidValue;
   CodecArgs a;
@@ -1405,6 +1551,10 @@ static int run_codec(void* x, void* msg, long long om, long long os, long long o
   else if (rot) DISPATCH_NCH(H, (launch_codec<PACK, NCH, bf16_t, true>(grid, st, a)));
   else if (w16 && x_f32) DISPATCH_NCH(H, (launch_codec<PACK, NCH, float, false, true>(grid, st, a)));
   else if (w16) DISPATCH_NCH(H, (launch_codec<PACK, NCH, bf16_t, false, true>(grid, st, a)));
+  else if (mxr && mx6 && x_f32) DISPATCH_NCH(H, (launch_codec<PACK, NCH, float, false, false, true, true>(grid, st, a)));
+  else if (mxr && mx6) DISPATCH_NCH(H, (launch_codec<PACK, NCH, bf16_t, false, false, true, true>(grid, st, a)));
+  else if (mxr && x_f32) DISPATCH_NCH(H, (launch_codec<PACK, NCH, float, false, false, false, true>(grid, st, a)));
+  else if (mxr) DISPATCH_NCH(H, (launch_codec<PACK, NCH, bf16_t, false, false, false, true>(grid, st, a)));
   else if (mx6 && x_f32) DISPATCH_NCH(H, (launch_codec<PACK, NCH, float, false, false, true>(grid, st, a)));
   else if (mx6) DISPATCH_NCH(H, (launch_codec<PACK, NCH, bf16_t, false, false, true>(grid, st, a)));
   else if (x_f32) DISPATCH_NCH(H, (launch_codec<PACK, NCH, float, false>(grid, st, a)));

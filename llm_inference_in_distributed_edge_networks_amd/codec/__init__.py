@@ -28,6 +28,8 @@ mixed_mxfp4_mxfp8      MXFP8 (E4M3)    MXFP4 (E2M1)    E8M0 / 32ch  configs 3-5 
 mxfp4_keep             native dtype    MXFP4           E8M0 / 32ch  Q1 with MX blocks instead of one scale
 (the three above)      with_mx_elem "e2m3" / "e3m2": their MXFP4    MXFP6 rows, 6.25 bits per element
                        rows as FP6 E2M3 / E3M2 codes                (gfx950 2xpk16 / pk32 fp6 converts)
+(the four above)       with_mx_rot "h32": their MX rows as the      the plain rows' bytes of y = H32 x / 4 per
+                       rotated twins of the same element type       32-channel block (Hadamard, quad DPP moves)
 rgroup                 head groups     --              per group    every 64-channel group (one head) its
                                                                     own max-abs scale and 2/4/8-bit width
 mixed_rgroup_int8      int8            head groups     token/group  config 5 (relevance-allocated widths
@@ -58,6 +60,11 @@ see ``wire.py``.  BASELINE config 1 ("fp16 pass-through") is ``passthrough`` wit
 7.5) or E3M2 (max 28) codes, 25 H / 32 bytes a row.  A modifier like ``with_native_wire``, not a new codec; not combined
 with a 16-bit native wire.
 
+``with_mx_rot(spec, "h32")`` (params key ``mx_rot``) puts a 32-point Hadamard transform in front of every MX block's
+quantizer and behind its dequantizer, at the plain row's bytes: one loud channel of a block no longer sets the scale
+that flushes the block's other 31.  It composes with ``with_mx_elem`` and is the one rotation that meets importance
+selection (``mixed_mxfp4_mxfp8``, ``mxfp4_keep``); not combined with a 16-bit native wire.
+
 ``fake_quant_fork(x, spec, B, S, variants, importances)`` is ``fake_quant`` for a whole list of (importance source, k)
 variants of one codec at once - the sweep's step between the shared prefix and the stacked suffix: one sort per
 source, one read of ``x``, one write per variant, bit-identical to the per-variant round trip (``fork_supported``: the
@@ -68,7 +75,8 @@ window (ascending importance, ties broken by position) are the lo class.
 """
 from . import plan  # noqa: F401  (codec.plan: the head-group bit plans)
 from .wire import (CODECS, CodecSpec, Layout, decode, encode, fake_quant, fake_quant_fork, fork_supported, get_codec,
-                   layout, message_bytes, select_mask, with_mx_elem, with_native_wire)
+                   layout, message_bytes, select_mask, with_mx_elem, with_mx_rot, with_native_wire)
 
 __all__ = ["CODECS", "CodecSpec", "Layout", "decode", "encode", "fake_quant", "fake_quant_fork", "fork_supported",
-           "get_codec", "layout", "message_bytes", "select_mask", "with_mx_elem", "with_native_wire"]
+           "get_codec", "layout", "message_bytes", "select_mask", "with_mx_elem", "with_mx_rot",
+           "with_native_wire"]

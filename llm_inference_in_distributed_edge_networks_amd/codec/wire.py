@@ -52,6 +52,18 @@ block's E8M0 scale; the clamp first: x / X reaches (7.5, 8) and (28, 32)).  With
 ``hi_fmt | lo_fmt << 8``, and ``decode`` refuses a message whose formats are not its spec's.  Not combined with a 16-bit
 native wire, and such specs are not served by ``fake_quant_fork``.
 
+Rotated MX rows.  ``with_mx_rot(spec, "h32")`` - a modifier too - resolves every MX class of a codec (the rows of
+``mxfp4``, ``mxfp8`` and ``mixed_mxfp4_mxfp8``, the lo rows of ``mxfp4_keep``; after ``with_mx_elem``) to its rotated twin
+(``FMT_MXFP4R`` = 13, ``FMT_MXFP8R`` = 14, ``FMT_MXFP6R`` = 15, ``FMT_MXBF6R`` = 16): the plain row's bytes, but codes
+and scale byte describe ``y = H32 x / 4`` of every 32-channel block, H32 the natural-order Sylvester matrix
+(``y_i = sum_j (-1)^popcount(i & j) x_j``) - one loud channel of a block is spread over all 32, so the block's scale no
+longer flushes its small channels.  Encode: five fp32 butterfly stages ``(a, b) -> (a + b, a - b)`` at channel strides
+1, 2, 4, 8, 16 (the lower index keeps the sum), one multiply by 0.25, then the plain row's quantizer.  Decode: the
+plain row's values, the same five stages, one multiply by 0.125 (H32 H32 = 32 I).  The decoder's sums are multiples of
+the grid quantum below 2^24 of them, so exact.  A block holding a NaN / Inf, or a finite one whose butterflies overflow
+(max-abs from about 2^123 up), stores byte 255 and decodes to 32 NaNs.  Header word 7 is ``hi_fmt | lo_fmt << 8``.  Not
+combined with a 16-bit native wire; such specs are not served by ``fake_quant_fork``.
+
 ``encode``/``decode`` run the gfx950 kernels of ``csrc/codec.hip`` for CUDA
 tensors and a bit-identical PyTorch implementation for CPU tensors.
 
@@ -78,12 +90,15 @@ FMT_F16, FMT_F16S = 9, 10   # 16-bit wires of NATIVE rows: IEEE binary16; binary
 FMT_MXFP6, FMT_MXBF6 = 11, 12   # MX rows of FP6 E2M3 / E3M2 codes (with_mx_elem)
 MX6_FORMATS = (FMT_MXFP6, FMT_MXBF6)
 MX_FORMATS = (FMT_MXFP4, FMT_MXFP8) + MX6_FORMATS
+FMT_MXFP4R, FMT_MXFP8R, FMT_MXFP6R, FMT_MXBF6R = 13, 14, 15, 16   # MX rows of the Hadamard-rotated blocks (with_mx_rot)
+MX_ROT_TWIN = {FMT_MXFP4: FMT_MXFP4R, FMT_MXFP8: FMT_MXFP8R, FMT_MXFP6: FMT_MXFP6R, FMT_MXBF6: FMT_MXBF6R}
 GRP_FORMATS = (FMT_GRP, FMT_GRPR)
 SC_TOKEN, SC_WINDOW, SC_CHANNEL, SC_NONE = 0, 1, 2, 3
 CH_MAXABS, CH_MEAN = 0, 1
 NATIVE = -1  # "keep in the activation dtype" (bf16 on GPU, fp32 in the CPU reference mode)
 NATIVE_WIRES = {"native": NATIVE, "bf16": FMT_BF16, "fp16": FMT_F16, "fp16s": FMT_F16S}   # with_native_wire
 MX_ELEMS = {"fp4": FMT_MXFP4, "e2m3": FMT_MXFP6, "e3m2": FMT_MXBF6}                         # with_mx_elem
+MX_ROTS = {"none": 0, "h32": 32}                                                            # with_mx_rot: block size
 
 
 @dataclass(frozen=True)
@@ -101,6 +116,7 @@ class CodecSpec:
     plan: tuple | None = None    # FMT_GRP / FMT_GRPR rows: bits (GROUP_BITS) of every 64-channel group (with_plan)
     native_wire: int = NATIVE    # row format of the NATIVE classes on the wire (with_native_wire); NATIVE: the dtype's
     mx_elem: int = FMT_MXFP4     # row format of the FMT_MXFP4 classes on the wire (with_mx_elem)
+    mx_rot: int = 0              # 32: the MX classes cross as their rotated twins (with_mx_rot); 0: as they are
 
 
 CODECS = {c.name: c for c in [
@@ -168,6 +184,8 @@ def with_native_wire(spec: CodecSpec, name: str) -> CodecSpec:
                          "to apply to")
     if name != "native" and spec.mx_elem != FMT_MXFP4:
         raise ValueError(f"native_wire {name!r} is not combined with 6-bit MX rows (mx_elem)")
+    if name != "native" and spec.mx_rot:
+        raise ValueError(f"native_wire {name!r} is not combined with rotated MX rows (mx_rot)")
     return spec if spec.native_wire == NATIVE_WIRES[name] else replace(spec, native_wire=NATIVE_WIRES[name])
 
 
@@ -184,6 +202,25 @@ def with_mx_elem(spec: CodecSpec, name: str) -> CodecSpec:
         if spec.native_wire != NATIVE:
             raise ValueError(f"mx_elem {name!r} is not combined with a 16-bit native wire (native_wire)")
     return spec if spec.mx_elem == MX_ELEMS[name] else replace(spec, mx_elem=MX_ELEMS[name])
+
+
+def has_mx_rows(spec: CodecSpec) -> bool:
+    return spec.hi_fmt in MX_FORMATS or spec.lo_fmt in MX_FORMATS
+
+
+def with_mx_rot(spec: CodecSpec, name: str) -> CodecSpec:
+    """The codec with its MX rows quantized in the basis of the 32-point Hadamard transform of every block: "none" (the
+    spec itself) | "h32" (module docstring).  Composes with ``with_mx_elem``.  A codec without MX rows takes "none"
+    only; rotated MX rows are not combined with a 16-bit native wire."""
+    from dataclasses import replace
+    if name not in MX_ROTS:
+        raise ValueError(f"mx_rot must be one of {tuple(MX_ROTS)}, got {name!r}")
+    if name != "none":
+        if not has_mx_rows(spec):
+            raise ValueError(f"codec {spec.name} has no MX rows: mx_rot {name!r} has nothing to apply to")
+        if spec.native_wire != NATIVE:
+            raise ValueError(f"mx_rot {name!r} is not combined with a 16-bit native wire (native_wire)")
+    return spec if spec.mx_rot == MX_ROTS[name] else replace(spec, mx_rot=MX_ROTS[name])
 
 
 def get_codec(name: str) -> CodecSpec:
@@ -257,8 +294,12 @@ def num_lo(spec: CodecSpec, ratio: float, S: int) -> int:
 
 
 def _resolve(fmt: int, spec: CodecSpec, native: int) -> int:
-    """A class's row format on the wire: the spec's, with its modifiers (native wire, MX element type) applied."""
-    return native if fmt == NATIVE else spec.mx_elem if fmt == FMT_MXFP4 else fmt
+    """A class's row format on the wire: the spec's, with its modifiers (native wire, MX element type, MX rotation)
+    applied."""
+    if fmt == NATIVE:
+        return native
+    fmt = spec.mx_elem if fmt == FMT_MXFP4 else fmt
+    return MX_ROT_TWIN.get(fmt, fmt) if spec.mx_rot else fmt
 
 
 @lru_cache(maxsize=256)
@@ -546,6 +587,25 @@ def _wht64(v: torch.Tensor) -> torch.Tensor:
     return v
 
 
+def _wht32(v: torch.Tensor) -> torch.Tensor:
+    """Unnormalised 32-point Walsh-Hadamard transform (Sylvester order) of the last dimension in fp32: the butterflies
+    (a, b) -> (a + b, a - b) at channel strides 1, 2, 4, 8, 16 in that order, the lower index keeping the sum - the
+    order and operations of csrc/codec.hip wht8 / wht_quad (4 and 8-bit rows) and wht32 (6-bit rows)."""
+    lead = v.shape[:-1]
+    for h in (1, 2, 4, 8, 16):
+        p = v.reshape(*lead, 32 // (2 * h), 2, h)
+        a, b = p[..., 0, :], p[..., 1, :]
+        v = torch.stack((a + b, a - b), -2).reshape(*lead, 32)
+    return v
+
+
+def _rot32(rows: torch.Tensor, scale: float) -> torch.Tensor:
+    """``scale`` H32 x of every 32-channel block of fp32 rows [n, H]: 0.25 before the quantizer, 0.125 after the
+    dequantizer (both exact multiplies, after the last add)."""
+    n, H = rows.shape
+    return (_wht32(rows.float().reshape(n, H // 32, 32)) * scale).reshape(n, H)
+
+
 def hadamard64(x: torch.Tensor) -> torch.Tensor:
     """y_g = H64 x_g / 8 for every 64-channel group of fp32 rows [n, H]: orthonormal, symmetric, its own inverse.
     The scaling by 1/8 is exact, so the only roundings are those of the 6 butterfly levels' fp32 adds."""
@@ -665,7 +725,12 @@ def _int_rows(fmt: int, per_byte: int) -> RowFormat:
     return RowFormat(lambda H, plan: H // per_byte, False, pack, unpack)
 
 
-def _mx_rows(fmt: int, code_bits: int) -> RowFormat:    # codes, then one E8M0 byte per 32 channels
+def _mx_rows(fmt: int, code_bits: int, rot: bool = False) -> RowFormat:    # codes, then one E8M0 byte per 32 channels
+    """``rot``: the rotated twin - the same bytes of the blocks rotated before the pack and back after the unpack."""
+    if rot:
+        return RowFormat(lambda H, plan: H * code_bits // 8 + H // 32, True,
+                         lambda rows, c: _mx_pack(_rot32(rows, 0.25), fmt),
+                         lambda raw, n, c: _rot32(_mx_unpack(raw, fmt, n, c.H), 0.125))
     return RowFormat(lambda H, plan: H * code_bits // 8 + H // 32, True,
                      lambda rows, c: _mx_pack(rows, fmt), lambda raw, n, c: _mx_unpack(raw, fmt, n, c.H))
 
@@ -684,6 +749,8 @@ ROW_FORMATS = {
     FMT_INT8: _int_rows(FMT_INT8, 1), FMT_INT4: _int_rows(FMT_INT4, 2), FMT_INT2: _int_rows(FMT_INT2, 4),
     FMT_MXFP4: _mx_rows(FMT_MXFP4, 4), FMT_MXFP8: _mx_rows(FMT_MXFP8, 8),
     FMT_MXFP6: _mx_rows(FMT_MXFP6, 6), FMT_MXBF6: _mx_rows(FMT_MXBF6, 6),
+    FMT_MXFP4R: _mx_rows(FMT_MXFP4, 4, True), FMT_MXFP8R: _mx_rows(FMT_MXFP8, 8, True),
+    FMT_MXFP6R: _mx_rows(FMT_MXFP6, 6, True), FMT_MXBF6R: _mx_rows(FMT_MXBF6, 6, True),
     FMT_GRP: _grp_rows(False), FMT_GRPR: _grp_rows(True),
     FMT_F16: RowFormat(lambda H, plan: 2 * H, True, lambda rows, c: _bytes(rows.to(torch.float16)),
                        lambda raw, n, c: raw.view(torch.float16).reshape(n, c.H).float()),
@@ -693,8 +760,9 @@ ROW_FORMATS = {
 
 
 def _fmt_word(spec: CodecSpec, L: Layout) -> int:
-    """Header word 7: the hi-row format; with 6-bit MX rows (with_mx_elem) the lo-row format too, in bits 8-15."""
-    return L.hi_fmt | L.lo_fmt << 8 if spec.mx_elem != FMT_MXFP4 else L.hi_fmt
+    """Header word 7: the hi-row format; with 6-bit or rotated MX rows (with_mx_elem, with_mx_rot) the lo-row format
+    too, in bits 8-15."""
+    return L.hi_fmt | L.lo_fmt << 8 if spec.mx_elem != FMT_MXFP4 or spec.mx_rot else L.hi_fmt
 
 
 def _header(spec: CodecSpec, L: Layout) -> torch.Tensor:
@@ -705,7 +773,8 @@ def _header(spec: CodecSpec, L: Layout) -> torch.Tensor:
 def _check_formats(spec: CodecSpec, L: Layout, msg: torch.Tensor | None = None) -> None:
     """decode's refusal of a message whose row formats are not the spec's: the layout's against the spec with its
     modifiers (any device, no read of the message), and the header's format word of a CPU message against the
-    layout's.  (The GPU kernels check the word of a message with 6-bit MX rows themselves and decode it to NaN.)"""
+    layout's.  (The GPU kernels check the word of a message with 6-bit or rotated MX rows themselves and decode it to
+    NaN.)"""
     for name, got, fmt in (("hi", L.hi_fmt, spec.hi_fmt), ("lo", L.lo_fmt, spec.lo_fmt)):
         want = (got if spec.native_wire == NATIVE and got in (FMT_BF16, FMT_F32) else spec.native_wire) \
             if fmt == NATIVE else _resolve(fmt, spec, NATIVE)
@@ -929,7 +998,7 @@ def fork_supported(spec: CodecSpec, selection: str = "ratio") -> bool:
     fixed k, NATIVE rows in the activation dtype (the codecs the sweeps run: ref_int4_global, int4_token, int8_token,
     int8_token_keep, mixed_int4_int8, mixed_int2_int8).  Everything else keeps the per-variant ``fake_quant``."""
     uses_kvar(spec, selection)       # an unknown selection: ValueError
-    return (selection == "ratio" and spec.native_wire == NATIVE and spec.mx_elem == FMT_MXFP4
+    return (selection == "ratio" and spec.native_wire == NATIVE and spec.mx_elem == FMT_MXFP4 and not spec.mx_rot
             and spec.scale_mode in (SC_TOKEN, SC_WINDOW)
             and (spec.hi_fmt, spec.qmax_hi) in _FORK_ROWS and (spec.lo_fmt, spec.qmax_lo) in _FORK_ROWS)
 

@@ -52,6 +52,8 @@ class Params:
                                              # with_native_wire); BASELINE config 1 literally: passthrough + "fp16"
     mx_elem: str = "fp4"                     # element type of a codec's MXFP4 rows: "fp4" (E2M1) | "e2m3" | "e3m2" (MXFP6
                                              # rows, 6.25 bits per element; codec/wire.py with_mx_elem)
+    mx_rot: str = "none"                     # "h32": a codec's MX rows quantize the 32-point Hadamard transform of
+                                             # every block (codec/wire.py with_mx_rot); "none": the blocks themselves
     sweep_fork: bool = False                 # sweeps: all (method, ratio) variants of a boundary layer from one
                                              # codec.fake_quant_fork pass (bit-identical to the per-variant path)
     lrp_engine: str = "auto"                 # relevance pass: "auto" (HIP engine on a GPU, autograd on the CPU) |
@@ -113,6 +115,11 @@ class Params:
             from .codec import wire   # an element type no codec knows, or one for a codec without MXFP4 rows: ValueError
             spec = wire.CODECS.get(self.codec) or wire.CODECS["passthrough"]
             wire.with_mx_elem(wire.with_native_wire(spec, self.native_wire), self.mx_elem)
+        if self.mx_rot != "none":
+            from .codec import wire   # a rotation no codec knows, or one for a codec without MX rows: ValueError
+            spec = wire.CODECS.get(self.codec) or wire.CODECS["passthrough"]
+            wire.with_mx_rot(wire.with_mx_elem(wire.with_native_wire(spec, self.native_wire), self.mx_elem),
+                             self.mx_rot)
 
 
 def resolve_device(p: Params) -> str:

@@ -6,7 +6,8 @@
     python tools/codec_bench.py --codecs mxfp8,mxfp4@e2m3,mxfp4@e3m2,mxfp4
 
 ``name@wire`` is codec ``name`` with its activation-dtype rows on the 16-bit wire ``wire`` (``with_native_wire``),
-``name@e2m3`` / ``name@e3m2`` with its MXFP4 rows as MXFP6 rows of that element type (``with_mx_elem``).
+``name@e2m3`` / ``name@e3m2`` with its MXFP4 rows as MXFP6 rows of that element type (``with_mx_elem``), ``name@rot``
+with its MX rows Hadamard-rotated (``with_mx_rot``); modifiers chain: ``mxfp4@e2m3@rot``.
 
 Every codec packs the same activations ([B * S, H], randn with one massive channel) into its own preallocated
 message (the pack kernel alone: selection and statistics run once, before) and decodes it into a preallocated
@@ -103,9 +104,11 @@ def main():
         x = x32.to(dtype)
         runs = {}
         for n in names:
-            base, mod = (n.split("@") + ["native"])[:2]
-            spec = C.with_mx_elem(C.get_codec(base), mod) if mod in W.MX_ELEMS else \
-                C.with_native_wire(C.get_codec(base), mod)
+            base, *mods = n.split("@")
+            spec = C.get_codec(base)
+            for mod in mods:
+                spec = C.with_mx_elem(spec, mod) if mod in W.MX_ELEMS else C.with_mx_rot(spec, "h32") if mod == "rot" \
+                    else C.with_native_wire(spec, mod)
             if C.wire.needs_plan(spec):
                 spec = C.wire.with_plan(spec, (a.plan_bits,) * (H // 64))
             L = C.layout(spec, B, S, H, C.wire.num_lo(spec, a.ratio, S), dtype)
