@@ -20,7 +20,28 @@
 
 enum { FMT_BF16 = 0, FMT_INT8 = 1, FMT_INT4 = 2, FMT_INT2 = 3, FMT_F32 = 4, FMT_MXFP4 = 5, FMT_MXFP8 = 6, FMT_GRP = 7,
        FMT_GRPR = 8, FMT_F16 = 9, FMT_F16S = 10, FMT_MXFP6 = 11, FMT_MXBF6 = 12,
-       FMT_MXFP4R = 13, FMT_MXFP8R = 14, FMT_MXFP6R = 15, FMT_MXBF6R = 16 };
+       FMT_MXFP4R = 13, FMT_MXFP8R = 14, FMT_MXFP6R = 15, FMT_MXBF6R = 16,
+       FMT_INT8O = 17, FMT_INT4O = 18, FMT_INT2O = 19 };
+// Outlier rows (FMT_INT8O / FMT_INT4O / FMT_INT2O; codec/wire.py with_outliers resolves the int classes of a per-token
+// codec to them): [the plain twin's code bytes][8 fp32 values][8 uint16 channels], the twin's bytes + OUT_TAIL.  The 8
+// channels with the largest abs_bits(x) (NaN > Inf > finite; ties to the lower channel), listed in that order, cross
+// with their exact bits; the row's scale (in the message's scale section, as for the twin) is tok_scale of the max|x|
+// of the OTHER channels and the codes are tok_code of the row with the 8 replaced by +0.  Decode: the twin's
+// tok_value, then pair r = 0 .. 7 overwrites its channel; a channel >= H in a received row decodes the row to NaN.
+// The code sections are multiples of 8 bytes (H % 32 == 0), so the tail is 4-byte aligned and every access to it is 4
+// or 2 bytes wide.  Messages with such rows run the OUT instantiations of pack_kernel / unpack_kernel (every such
+// branch under `if constexpr (OUT)`; SC_TOKEN only, not next to head-group, 16-bit, 6-bit or rotated rows), so the
+// instantiations every other codec runs keep their instruction stream.  Header word 7 is hi_fmt | lo_fmt << 8 and
+// unpack_kernel<OUT> decodes a message that says otherwise to NaN.  The selection: out_extract, the patch: out_patch.
+enum { OUT_K = 8, OUT_TAIL = 6 * OUT_K };
+__device__ __forceinline__ bool is_out_fmt(int fmt) { return fmt >= FMT_INT8O && fmt <= FMT_INT2O; }
+template <bool OUT>
+__device__ __forceinline__ int out_twin(int fmt) {   // an outlier row's plain twin, any other format itself
+  if constexpr (OUT) {
+    if (is_out_fmt(fmt)) return fmt - (FMT_INT8O - FMT_INT8);
+  }
+  return fmt;
+}
 // 16-bit wire formats of the rows a codec keeps in the activation dtype (codec/wire.py with_native_wire: the NATIVE
 // class of a codec resolves to one of them instead of the activation dtype, so fp32 activations cross at 2 B per
 // element).  FMT_BF16 (above): round to nearest even.  FMT_F16: IEEE binary16, the fp32 value converted with round to
@@ -113,8 +134,11 @@ struct CodecArgs {
   int grp_code_bytes;           // FMT_GRP / FMT_GRPR: sum over groups of 8 b_g (row = codes + 4 G scale bytes)
 };
 
-template <bool W16, bool MX6, bool MXR = false>
+template <bool W16, bool MX6, bool MXR = false, bool OUT = false>
 __device__ __forceinline__ int fmt_row_bytes(int fmt, int H) {
+  if constexpr (OUT) {   // an outlier row has the bytes of its plain twin and the tail
+    if (is_out_fmt(fmt)) return (fmt == FMT_INT8O ? H : fmt == FMT_INT4O ? H / 2 : H / 4) + OUT_TAIL;
+  }
   if constexpr (W16) {
     if (fmt == FMT_F16) return 2 * H;
     if (fmt == FMT_F16S) return 2 * H + 4;
@@ -132,12 +156,12 @@ __device__ __forceinline__ int fmt_row_bytes(int fmt, int H) {
   return fmt == FMT_F32 ? 4 * H : fmt == FMT_BF16 ? 2 * H : fmt == FMT_INT8 ? H : fmt == FMT_INT4 ? H / 2 :
          fmt == FMT_MXFP4 ? H / 2 + H / 32 : fmt == FMT_MXFP8 ? H + H / 32 : H / 4;
 }
-template <bool ROT, bool W16, bool MX6, bool MXR = false>
+template <bool ROT, bool W16, bool MX6, bool MXR = false, bool OUT = false>
 __device__ __forceinline__ int row_bytes(const CodecArgs& a, int fmt) {
   if constexpr (ROT) {
     if (fmt == FMT_GRPR) return a.grp_code_bytes + 4 * (a.H / 64);
   }
-  return fmt == FMT_GRP ? a.grp_code_bytes + 4 * (a.H / 64) : fmt_row_bytes<W16, MX6, MXR>(fmt, a.H);
+  return fmt == FMT_GRP ? a.grp_code_bytes + 4 * (a.H / 64) : fmt_row_bytes<W16, MX6, MXR, OUT>(fmt, a.H);
 }
 // Formats whose rows carry their own scales (or none): no entry in the message's scale section.  A macro, and the
 // rotated format joined with `|`: the compiler simplifies the body of an inlined function on its own first, and the
@@ -307,19 +331,19 @@ __device__ __forceinline__ void kvar_prefix(const CodecArgs& a, int b, int& Kb, 
 // among the class's rows of its window (lo_prefix), the class's rows of the windows before (b k / b (S - k) for fixed
 // k, the k vector's prefix sum for variable k, whose hi section starts right after the Sum k lo rows).
 struct RowSlot { uint8_t* p; int fmt, qmax, b; };
-template <bool ROT, bool W16, bool MX6, bool MXR = false>
+template <bool ROT, bool W16, bool MX6, bool MXR = false, bool OUT = false>
 __device__ __forceinline__ RowSlot row_slot(const CodecArgs& a, int row) {
   const int b = row / a.S, j = row - b * a.S;
   const uint32_t* mask = (const uint32_t*)(a.msg + a.off_mask) + (size_t)b * a.mw;
   bool is_lo;
   const int slot_lo = lo_prefix(mask, a.mw, j, is_lo);
   const int fmt = is_lo ? a.lo_fmt : a.hi_fmt;
-  const int rb = row_bytes<ROT, W16, MX6, MXR>(a, fmt);
+  const int rb = row_bytes<ROT, W16, MX6, MXR, OUT>(a, fmt);
   uint8_t* p;
   if (a.off_kvec >= 0) {
     int Kb, Kt;
     kvar_prefix(a, b, Kb, Kt);
-    const long long off_hi = a.off_lo + (((long long)Kt * row_bytes<ROT, W16, MX6, MXR>(a, a.lo_fmt) + 15) & ~15ll);
+    const long long off_hi = a.off_lo + (((long long)Kt * row_bytes<ROT, W16, MX6, MXR, OUT>(a, a.lo_fmt) + 15) & ~15ll);
     p = is_lo ? a.msg + a.off_lo + ((size_t)Kb + slot_lo) * rb
               : a.msg + off_hi + ((size_t)b * a.S - Kb + (j - slot_lo)) * rb;
   } else {
@@ -861,14 +885,152 @@ __device__ __forceinline__ void mx6_pack_row(uint8_t* __restrict__ row, int H, i
   }
 }
 
-template <int NCH, class T, bool ROT = false, bool W16 = false, bool MX6 = false, bool MXR = false>
+// ---- Outlier rows: the 8 largest channels of a row, exactly ----------------------------------------------------------
+// The wave-wide maximum of an unsigned value as a wave-uniform (scalar register) result, on the VALU's DPP operand
+// path: an inclusive max-scan of each 16-lane row (row_shr 1, 2, 4, 8: a lane whose source lies outside its row keeps
+// `old`, 0, the identity), the total of rows 0 / 2 into rows 1 / 3 (row_bcast15 under row mask 0xa), that of rows 0-1
+// into rows 2-3 (row_bcast31 under row mask 0xc): lane 63 holds the maximum of all 64, read with v_readlane_b32.  Six
+// v_max_u32 with a DPP operand against wave_umax's six ds_bpermute_b32 round trips through the LDS crossbar, and the
+// result is scalar: compares take it as a scalar operand and what is derived from it (the winner's chunk, element and
+// lane) is wave-uniform, so the branches on it are scalar branches.  Every lane of the wave must be active.
+enum { DPP_ROW_SHR = 0x110, DPP_ROW_BCAST15 = 0x142, DPP_ROW_BCAST31 = 0x143 };
+template <int CTRL, int ROWS = 0xf>
+__device__ __forceinline__ uint32_t dpp_umax(uint32_t x) {
+  return umax(x, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, CTRL, ROWS, 0xf, false));
+}
+__device__ __forceinline__ uint32_t wave_umax_s(uint32_t x) {
+  x = dpp_umax<DPP_ROW_SHR + 1>(x);
+  x = dpp_umax<DPP_ROW_SHR + 2>(x);
+  x = dpp_umax<DPP_ROW_SHR + 4>(x);
+  x = dpp_umax<DPP_ROW_SHR + 8>(x);
+  x = dpp_umax<DPP_ROW_BCAST15, 0xa>(x);
+  x = dpp_umax<DPP_ROW_BCAST31, 0xc>(x);
+  return (uint32_t)__builtin_amdgcn_readlane((int)x, 63);
+}
+__device__ __forceinline__ uint32_t lane_bits(uint32_t x, int l) { return (uint32_t)__builtin_amdgcn_readlane((int)x, l); }
+
+// A lane's best live element of one chunk.  key: bits | 2^31 of a live element (above every taken one, ordered by
+// abs_bits), 0 of a taken one - bit e of `taken` set: element e has left the row, or lies past H.  The first of equal
+// keys wins (ascending e: the lower channel).  kr = 512 c + e, the element's channel less 8 lane.
+__device__ __forceinline__ void out_scan8(const float (&v)[8], uint32_t taken, int c, uint32_t& ka, uint32_t& kr) {
+  ka = 0;
+  kr = 0;
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    const uint32_t key = (taken >> e) & 1u ? 0u : (__float_as_uint(v[e]) | 0x80000000u);
+    if (key > ka) { ka = key; kr = (uint32_t)(c * 512 + e); }
+  }
+}
+// pack_kernel's selection for an outlier row, held as everywhere 8 consecutive channels per lane and chunk in
+// v[NCH][8]: writes the row's tail ([8 fp32 values][8 uint16 channels] at `tail`, lanes 0 .. 7, pair r on lane r),
+// replaces the 8 channels by +0 in v and returns the bits of the max|x| of the rest.  No LDS, no scratch, no register
+// indexed by data.  The split that was built: every lane caches, per chunk, its best live (key, place) pair, so a round
+// is (1) the lane's best over its NCH cached pairs, (2) two wave_umax_s - the key, then ~channel among the lanes
+// holding it: the lowest such channel - which give the winner wave-uniformly, (3) under scalar branches on the winner's
+// chunk: its exact bits (a select over the chunk's 8 registers by the uniform element index, read from the owning lane
+// with v_readlane_b32), its bit in the owner's `taken` mask, and a rescan of THAT chunk's 8 registers only.  The
+// registers themselves stay as loaded until the 8 rounds are over - a taken element is masked, not zeroed, so a zero
+// that was taken cannot win again against the live zeros of an all-zero rest - and the rescan runs on all lanes
+// unpredicated: only the owner's mask changed, every other lane recomputes what it had, at the same issue cost as a
+// predicated one.  A round so rescans 8 registers, not the lane's 8 NCH.  A lane-local pre-selection of 8 candidates
+// (fewer wave-wide rounds) was not built: it needs a sorted insert per element, 8 compares each.
+// After round 8 the cached keys are those of the rest: one more wave_umax_s is its max-abs, with no second pass.
+// Channels past H (a partial last chunk: zeros in v) start as taken; H >= 32 leaves at least 24 live channels.
+template <int NCH>
+__device__ __forceinline__ uint32_t out_extract(float (&v)[NCH][8], int H, uint8_t* __restrict__ tail) {
+  const int lane = threadIdx.x & 63;
+  uint32_t taken[(NCH + 3) / 4], ca[NCH], cr[NCH];   // taken: 8 bits a chunk, 4 chunks a word
+#pragma unroll
+  for (int w = 0; w < (NCH + 3) / 4; ++w) taken[w] = 0;
+#pragma unroll
+  for (int c = 0; c < NCH; ++c) {
+    if ((c * 64 + lane) * 8 >= H) taken[c >> 2] |= 0xffu << (8 * (c & 3));
+    out_scan8(v[c], taken[c >> 2] >> (8 * (c & 3)), c, ca[c], cr[c]);
+  }
+  uint32_t myval = 0, myidx = 0;
+#pragma unroll
+  for (int r = 0; r < OUT_K; ++r) {
+    uint32_t ka = ca[0], kr = cr[0];
+#pragma unroll
+    for (int c = 1; c < NCH; ++c)
+      if (ca[c] > ka) { ka = ca[c]; kr = cr[c]; }
+    const uint32_t m = wave_umax_s(ka);
+    const uint32_t win = ~wave_umax_s(ka == m ? ~((uint32_t)lane * 8 + kr) : 0u);   // the winner's channel
+    const int wc = (int)(win >> 9), we = (int)(win & 7), wl = (int)(win >> 3) & 63;
+    uint32_t val = 0;
+#pragma unroll
+    for (int c = 0; c < NCH; ++c) {
+      if (wc != c) continue;
+      float x = v[c][0];
+#pragma unroll
+      for (int e = 1; e < 8; ++e) x = we == e ? v[c][e] : x;
+      val = lane_bits(__float_as_uint(x), wl);
+      if (lane == wl) taken[c >> 2] |= 1u << (8 * (c & 3) + we);
+      out_scan8(v[c], taken[c >> 2] >> (8 * (c & 3)), c, ca[c], cr[c]);
+    }
+    if (lane == r) { myval = val; myidx = win; }
+  }
+  uint32_t ka = ca[0];
+#pragma unroll
+  for (int c = 1; c < NCH; ++c) ka = umax(ka, ca[c]);
+  const uint32_t amb = wave_umax_s(ka) & 0x7fffffffu;   // no live element on any lane: 0
+#pragma unroll
+  for (int c = 0; c < NCH; ++c)
+#pragma unroll
+    for (int e = 0; e < 8; ++e)
+      if ((taken[c >> 2] >> (8 * (c & 3) + e)) & 1u) v[c][e] = 0.f;
+  if (lane < OUT_K) {
+    *(uint32_t*)(tail + 4 * lane) = myval;
+    *(uint16_t*)(tail + 4 * OUT_K + 2 * lane) = (uint16_t)myidx;
+  }
+  return amb;
+}
+
+// unpack_kernel's side: the 8 (channel, value) pairs of a row's tail, read once by lanes 0 .. 7 and held wave-uniformly
+// (v_readlane_b32 with constant lanes: 16 scalar registers), and `bad`: a channel >= H among them - the row decodes to
+// NaN.  out_patch overwrites, in the 8 decoded values of chunk c on this lane, the channels of the pairs that lie in
+// that chunk - a scalar branch per pair, then 8 compares of the pair's place on the lane against constants - in pair
+// order, so the last of two pairs naming one channel holds, as on the CPU.  It runs before the chunk's store8: no
+// address is formed from a message's channel, and nothing is stored twice.
+struct OutPairs { uint32_t idx[OUT_K], val[OUT_K]; bool bad; };
+__device__ __forceinline__ OutPairs out_load(const uint8_t* __restrict__ tail, int H) {
+  const int lane = threadIdx.x & 63;
+  uint32_t val = 0, idx = 0;
+  if (lane < OUT_K) {
+    val = *(const uint32_t*)(tail + 4 * lane);
+    idx = *(const uint16_t*)(tail + 4 * OUT_K + 2 * lane);
+  }
+  OutPairs p;
+  p.bad = false;
+#pragma unroll
+  for (int r = 0; r < OUT_K; ++r) {
+    p.idx[r] = lane_bits(idx, r);
+    p.val[r] = lane_bits(val, r);
+    p.bad |= p.idx[r] >= (uint32_t)H;
+  }
+  return p;
+}
+__device__ __forceinline__ void out_patch(float (&o)[8], const OutPairs& p, int c) {
+  const uint32_t base = (uint32_t)(c * 64 + (threadIdx.x & 63)) * 8;
+#pragma unroll
+  for (int r = 0; r < OUT_K; ++r) {
+    if ((int)(p.idx[r] >> 9) != c) continue;
+    const uint32_t at = p.idx[r] - base;   // 0 .. 7 on the lane holding the channel
+#pragma unroll
+    for (int e = 0; e < 8; ++e) o[e] = at == (uint32_t)e ? __uint_as_float(p.val[r]) : o[e];
+  }
+  if (p.bad) fill8(o, __builtin_nanf(""));
+}
+
+template <int NCH, class T, bool ROT = false, bool W16 = false, bool MX6 = false, bool MXR = false, bool OUT = false>
 __global__ __launch_bounds__(256) void pack_kernel(CodecArgs a) {
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= a.B * a.S) return;
   const int lane = threadIdx.x & 63;
-  const RowSlot rs = row_slot<ROT, W16, MX6, MXR>(a, row);
+  const RowSlot rs = row_slot<ROT, W16, MX6, MXR, OUT>(a, row);
   uint8_t* dst = rs.p;
-  const int fmt = rs.fmt, qmax = rs.qmax, b = rs.b;
+  const bool orow = OUT && is_out_fmt(rs.fmt);   // an outlier row: fmt is its plain twin's
+  const int fmt = out_twin<OUT>(rs.fmt), qmax = rs.qmax, b = rs.b;
   float v[NCH][8];
   load_row8<NCH>((const T*)a.x + (size_t)row * a.H, a.H, v);
   float* scales = (float*)(a.msg + a.off_scale);
@@ -880,11 +1042,22 @@ __global__ __launch_bounds__(256) void pack_kernel(CodecArgs a) {
   if (!raw) {
     if (a.scale_mode == SC_TOKEN) {
       uint32_t amb = 0;
+      if constexpr (OUT) {   // an outlier row: its 8 outliers leave v for the row's tail, the max-abs is the rest's
+        if (orow) {
+          amb = out_extract<NCH>(v, a.H, dst + fmt_row_bytes<false, false>(fmt, a.H));
+        } else {
 #pragma unroll
-      for (int c = 0; c < NCH; ++c)
+          for (int c = 0; c < NCH; ++c) amb = umax(amb, umax8(v[c]));
+          amb = wave_umax(amb);
+        }
+      } else {
 #pragma unroll
-        for (int e = 0; e < 8; ++e) amb = umax(amb, abs_bits(v[c][e]));
-      const float am = __uint_as_float(wave_umax(amb));   // NaN / Inf if the row holds one: s non-finite
+        for (int c = 0; c < NCH; ++c)
+#pragma unroll
+          for (int e = 0; e < 8; ++e) amb = umax(amb, abs_bits(v[c][e]));
+        amb = wave_umax(amb);
+      }
+      const float am = __uint_as_float(amb);   // NaN / Inf if the row (an outlier row: its rest) holds one: s non-finite
       const float s = tok_scale(am, qmax);
       if (lane == 0) scales[row] = s;
       inv = tok_inv(am, s);
@@ -1053,14 +1226,15 @@ __device__ __forceinline__ void mx6_unpack_row(const uint8_t* __restrict__ row, 
   }
 }
 
-template <int NCH, class T, bool ROT = false, bool W16 = false, bool MX6 = false, bool MXR = false>
+template <int NCH, class T, bool ROT = false, bool W16 = false, bool MX6 = false, bool MXR = false, bool OUT = false>
 __global__ __launch_bounds__(256) void unpack_kernel(CodecArgs a) {
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= a.B * a.S) return;
   const int lane = threadIdx.x & 63;
-  const RowSlot rs = row_slot<ROT, W16, MX6, MXR>(a, row);
+  const RowSlot rs = row_slot<ROT, W16, MX6, MXR, OUT>(a, row);
   const uint8_t* src = rs.p;
-  const int fmt = rs.fmt, qmax = rs.qmax, b = rs.b;
+  const bool orow = OUT && is_out_fmt(rs.fmt);   // an outlier row: fmt is its plain twin's
+  const int fmt = out_twin<OUT>(rs.fmt), qmax = rs.qmax, b = rs.b;
   const float* scales = (const float*)(a.msg + a.off_scale);
   float s = 0.f;
   if (!SELF_SCALED(ROT, W16, MX6, MXR, fmt)) {
@@ -1068,8 +1242,8 @@ __global__ __launch_bounds__(256) void unpack_kernel(CodecArgs a) {
     else if (a.scale_mode == SC_WINDOW) s = scales[b];
   }
   T* out = (T*)a.x + (size_t)row * a.H;
-  if constexpr (MX6 || MXR) {
-    // header word 7 of a message with 6-bit or rotated MX rows names both classes' formats; one that disagrees with the
+  if constexpr (MX6 || MXR || OUT) {
+    // header word 7 of a message with 6-bit, rotated MX or outlier rows names both classes' formats; one that disagrees with the
     // formats this launch was given (encoded with another element type, or without the modifier) decodes to NaN - loud
     if (((const int*)a.msg)[7] != (a.hi_fmt | a.lo_fmt << 8)) {
       float o[8];
@@ -1099,6 +1273,10 @@ __global__ __launch_bounds__(256) void unpack_kernel(CodecArgs a) {
   float p16 = 1.f;   // FMT_F16S: the row's p (FMT_F16: 1, an exact multiply)
   if constexpr (W16) {
     if (fmt == FMT_F16S) p16 = *(const float*)(src + 2 * a.H);
+  }
+  OutPairs op;
+  if constexpr (OUT) {
+    if (orow) op = out_load(src + fmt_row_bytes<false, false>(fmt, a.H), a.H);   // wave-uniform: the row's format
   }
 #pragma unroll
   for (int c = 0; c < NCH; ++c) {
@@ -1181,6 +1359,9 @@ __global__ __launch_bounds__(256) void unpack_kernel(CodecArgs a) {
         const float sc = scales[(size_t)b * a.H + col + e];
         o[e] = (a.ch_kind == CH_MEAN || qmax == 1) ? qf * sc : qf * sc / (float)qmax;
       }
+    }
+    if constexpr (OUT) {
+      if (orow) out_patch(o, op, c);
     }
     store8(out + col, o);
   }
@@ -1513,10 +1694,10 @@ EDGE_API int edge_rowmax(const float* in, float* out, int R, int H, hipStream_t 
 // A message with FMT_GRPR rows goes to the ROT instantiations (which handle every other format too).
 static bool has_fmt(int hi_fmt, int lo_fmt, int fmt) { return hi_fmt == fmt || lo_fmt == fmt; }
 
-template <bool PACK, int NCH, class T, bool ROT, bool W16 = false, bool MX6 = false, bool MXR = false>
+template <bool PACK, int NCH, class T, bool ROT, bool W16 = false, bool MX6 = false, bool MXR = false, bool OUT = false>
 static void launch_codec(dim3 grid, hipStream_t st, const CodecArgs& a) {
-  if constexpr (PACK) hipLaunchKernelGGL((pack_kernel<NCH, T, ROT, W16, MX6, MXR>), grid, dim3(256), 0, st, a);
-  else hipLaunchKernelGGL((unpack_kernel<NCH, T, ROT, W16, MX6, MXR>), grid, dim3(256), 0, st, a);
+  if constexpr (PACK) hipLaunchKernelGGL((pack_kernel<NCH, T, ROT, W16, MX6, MXR, OUT>), grid, dim3(256), 0, st, a);
+  else hipLaunchKernelGGL((unpack_kernel<NCH, T, ROT, W16, MX6, MXR, OUT>), grid, dim3(256), 0, st, a);
 }
 
 // edge_pack / edge_unpack: argument checks, CodecArgs and the (ROT | W16 | plain) x activation dtype x NCH dispatch.
@@ -1524,6 +1705,8 @@ static void launch_codec(dim3 grid, hipStream_t st, const CodecArgs& a) {
 // together with FMT_GRPR rows it is rejected before anything is launched.  A message with FMT_MXFP6 / FMT_MXBF6 rows goes
 // to the MX6 instantiations; together with FMT_GRPR, FMT_F16 or FMT_F16S rows it is rejected the same way.  A message
 // with rotated MX rows goes to the MXR instantiations - MXR x MX6 when one of them is 6-bit - under the same rejections.
+// A message with outlier rows goes to the OUT instantiations; with any scale mode but SC_TOKEN, or next to head-group,
+// 16-bit, 6-bit or rotated rows, it is rejected before anything is launched.
 template <bool PACK>
 static int run_codec(void* x, void* msg, long long om, long long os, long long oh, long long ol, long long okv,
                      long long opl, int B, int S, int H, int k, int hi_fmt, int lo_fmt, int scale_mode, int qmax_hi,
@@ -1534,7 +1717,11 @@ static int run_codec(void* x, void* msg, long long om, long long os, long long o
   const bool mxr6 = has_fmt(hi_fmt, lo_fmt, FMT_MXFP6R) || has_fmt(hi_fmt, lo_fmt, FMT_MXBF6R);
   const bool mxr = mxr6 || has_fmt(hi_fmt, lo_fmt, FMT_MXFP4R) || has_fmt(hi_fmt, lo_fmt, FMT_MXFP8R);
   const bool mx6 = mxr6 || has_fmt(hi_fmt, lo_fmt, FMT_MXFP6) || has_fmt(hi_fmt, lo_fmt, FMT_MXBF6);
+  const bool out = has_fmt(hi_fmt, lo_fmt, FMT_INT8O) || has_fmt(hi_fmt, lo_fmt, FMT_INT4O) ||
+                   has_fmt(hi_fmt, lo_fmt, FMT_INT2O);
   if ((rot && w16) || ((mx6 || mxr) && (rot || w16))) return (int)hipErrorInvalidValue;
+  if (out && (rot || w16 || mx6 || mxr || has_fmt(hi_fmt, lo_fmt, FMT_GRP) || scale_mode != SC_TOKEN))
+    return (int)hipErrorInvalidValue;
   if ((rot || has_fmt(hi_fmt, lo_fmt, FMT_GRP)) && (H % 64 || opl < 0 || grp_code_bytes <= 0))
     return (int)hipErrorInvalidValue;
   CodecArgs a;
@@ -1557,6 +1744,8 @@ static int run_codec(void* x, void* msg, long long om, long long os, long long o
   else if (mxr) DISPATCH_NCH(H, (launch_codec<PACK, NCH, bf16_t, false, false, false, true>(grid, st, a)));
   else if (mx6 && x_f32) DISPATCH_NCH(H, (launch_codec<PACK, NCH, float, false, false, true>(grid, st, a)));
   else if (mx6) DISPATCH_NCH(H, (launch_codec<PACK, NCH, bf16_t, false, false, true>(grid, st, a)));
+  else if (out && x_f32) DISPATCH_NCH(H, (launch_codec<PACK, NCH, float, false, false, false, false, true>(grid, st, a)));
+  else if (out) DISPATCH_NCH(H, (launch_codec<PACK, NCH, bf16_t, false, false, false, false, true>(grid, st, a)));
   else if (x_f32) DISPATCH_NCH(H, (launch_codec<PACK, NCH, float, false>(grid, st, a)));
   else DISPATCH_NCH(H, (launch_codec<PACK, NCH, bf16_t, false>(grid, st, a)));
   return (int)hipGetLastError();

@@ -30,6 +30,8 @@ mxfp4_keep             native dtype    MXFP4           E8M0 / 32ch  Q1 with MX b
                        rows as FP6 E2M3 / E3M2 codes                (gfx950 2xpk16 / pk32 fp6 converts)
 (the four above)       with_mx_rot "h32": their MX rows as the      the plain rows' bytes of y = H32 x / 4 per
                        rotated twins of the same element type       32-channel block (Hadamard, quad DPP moves)
+(the int rows above)   with_outliers "top8": the int8 / int4 /      the row's 8 largest channels cross as exact
+                       int2 rows of the per-token codecs            fp32 beside it; the scale is the rest's
 rgroup                 head groups     --              per group    every 64-channel group (one head) its
                                                                     own max-abs scale and 2/4/8-bit width
 mixed_rgroup_int8      int8            head groups     token/group  config 5 (relevance-allocated widths
@@ -65,6 +67,12 @@ quantizer and behind its dequantizer, at the plain row's bytes: one loud channel
 that flushes the block's other 31.  It composes with ``with_mx_elem`` and is the one rotation that meets importance
 selection (``mixed_mxfp4_mxfp8``, ``mxfp4_keep``); not combined with a 16-bit native wire.
 
+``with_outliers(spec, "top8")`` (params key ``outliers``) is the per-token int rows' answer to massive activations
+(LLM.int8 / SpQR): the 8 channels of a row with the largest magnitude cross exactly, as 8 fp32 values and 8 uint16
+channels after the row's codes (48 bytes a row), and the row's scale is the max-abs of the other H - 8 channels - one
+loud channel no longer rounds the rest of an int4 / int2 row to zero.  For ``int4_token``, ``int8_token``,
+``mixed_int4_int8``, ``mixed_int2_int8`` and ``int8_token_keep``; not combined with the other modifiers.
+
 ``fake_quant_fork(x, spec, B, S, variants, importances)`` is ``fake_quant`` for a whole list of (importance source, k)
 variants of one codec at once - the sweep's step between the shared prefix and the stacked suffix: one sort per
 source, one read of ``x``, one write per variant, bit-identical to the per-variant round trip (``fork_supported``: the
@@ -75,8 +83,8 @@ window (ascending importance, ties broken by position) are the lo class.
 """
 from . import plan  # noqa: F401  (codec.plan: the head-group bit plans)
 from .wire import (CODECS, CodecSpec, Layout, decode, encode, fake_quant, fake_quant_fork, fork_supported, get_codec,
-                   layout, message_bytes, select_mask, with_mx_elem, with_mx_rot, with_native_wire)
+                   layout, message_bytes, select_mask, with_mx_elem, with_mx_rot, with_native_wire, with_outliers)
 
 __all__ = ["CODECS", "CodecSpec", "Layout", "decode", "encode", "fake_quant", "fake_quant_fork", "fork_supported",
            "get_codec", "layout", "message_bytes", "select_mask", "with_mx_elem", "with_mx_rot",
-           "with_native_wire"]
+           "with_native_wire", "with_outliers"]

@@ -64,6 +64,27 @@ the grid quantum below 2^24 of them, so exact.  A block holding a NaN / Inf, or 
 (max-abs from about 2^123 up), stores byte 255 and decodes to 32 NaNs.  Header word 7 is ``hi_fmt | lo_fmt << 8``.  Not
 combined with a 16-bit native wire; such specs are not served by ``fake_quant_fork``.
 
+Outlier rows.  ``with_outliers(spec, "top8")`` - a modifier too - resolves every ``FMT_INT8`` / ``FMT_INT4`` /
+``FMT_INT2`` class of a per-token codec (``int4_token``, ``int8_token``, ``mixed_int4_int8``, ``mixed_int2_int8``,
+``int8_token_keep``) to its outlier twin (``FMT_INT8O`` = 17, ``FMT_INT4O`` = 18, ``FMT_INT2O`` = 19), the LLM.int8 /
+SpQR remedy for massive activations: a row's one scale is ``max|x| / qmax``, so one loud channel rounds the other
+H - 1 to zero at 4 or 2 bits.  Row = ``[the plain twin's code bytes][8 fp32 values][8 uint16 channels]``, the twin's
+bytes + 48 (the code sections are multiples of 8 bytes, the tail is 4-byte aligned); the per-token scale stays in the
+message's scale section.  On both sides:
+
+1. the 8 outliers are the channels with the largest ``abs_bits(x)`` - the unsigned bit pattern of ``|x|``, the order of
+   the codec's max-abs: NaN > Inf > finite - ties going to the lower channel, listed in that order;
+2. a stored value is the activation's exact bits as fp32 (-0 stays -0);
+3. the 8 channels are replaced by +0, the scale is ``max|rest| / qmax`` and the codes are the plain twin's of the rest;
+4. decode is the plain twin's, then pair 0 .. 7 overwrites its channel.
+
+So an all-zero row lists channels 0 .. 7 with value 0; up to 8 non-finite values cross exactly and the rest of the row
+stays finite; from the 9th on the rest's scale is non-finite and the rest decodes non-finite - loud, not clipped; a
+channel >= H in a received row decodes that whole row to NaN.  The count is fixed by the format (8), not an argument.
+Header word 7 is ``hi_fmt | lo_fmt << 8``.  Not for per-window / per-channel scales (``ref_int4_global`` stays the
+reference's Q1 bit for bit), not for codecs with head-group rows, not combined with a 16-bit native wire, ``mx_elem``
+or ``mx_rot``; such specs are not served by ``fake_quant_fork``.
+
 ``encode``/``decode`` run the gfx950 kernels of ``csrc/codec.hip`` for CUDA
 tensors and a bit-identical PyTorch implementation for CPU tensors.
 
@@ -92,6 +113,9 @@ MX6_FORMATS = (FMT_MXFP6, FMT_MXBF6)
 MX_FORMATS = (FMT_MXFP4, FMT_MXFP8) + MX6_FORMATS
 FMT_MXFP4R, FMT_MXFP8R, FMT_MXFP6R, FMT_MXBF6R = 13, 14, 15, 16   # MX rows of the Hadamard-rotated blocks (with_mx_rot)
 MX_ROT_TWIN = {FMT_MXFP4: FMT_MXFP4R, FMT_MXFP8: FMT_MXFP8R, FMT_MXFP6: FMT_MXFP6R, FMT_MXBF6: FMT_MXBF6R}
+FMT_INT8O, FMT_INT4O, FMT_INT2O = 17, 18, 19   # per-token int rows + the row's 8 largest channels exact (with_outliers)
+OUT_TWIN = {FMT_INT8: FMT_INT8O, FMT_INT4: FMT_INT4O, FMT_INT2: FMT_INT2O}
+OUT_K, OUT_TAIL = 8, 48     # outliers of such a row; bytes of its tail: 8 fp32 values, 8 uint16 channels
 GRP_FORMATS = (FMT_GRP, FMT_GRPR)
 SC_TOKEN, SC_WINDOW, SC_CHANNEL, SC_NONE = 0, 1, 2, 3
 CH_MAXABS, CH_MEAN = 0, 1
@@ -99,6 +123,7 @@ NATIVE = -1  # "keep in the activation dtype" (bf16 on GPU, fp32 in the CPU refe
 NATIVE_WIRES = {"native": NATIVE, "bf16": FMT_BF16, "fp16": FMT_F16, "fp16s": FMT_F16S}   # with_native_wire
 MX_ELEMS = {"fp4": FMT_MXFP4, "e2m3": FMT_MXFP6, "e3m2": FMT_MXBF6}                         # with_mx_elem
 MX_ROTS = {"none": 0, "h32": 32}                                                            # with_mx_rot: block size
+OUTLIERS = {"none": 0, "top8": OUT_K}                                                       # with_outliers: count
 
 
 @dataclass(frozen=True)
@@ -117,6 +142,7 @@ class CodecSpec:
     native_wire: int = NATIVE    # row format of the NATIVE classes on the wire (with_native_wire); NATIVE: the dtype's
     mx_elem: int = FMT_MXFP4     # row format of the FMT_MXFP4 classes on the wire (with_mx_elem)
     mx_rot: int = 0              # 32: the MX classes cross as their rotated twins (with_mx_rot); 0: as they are
+    outliers: int = 0            # 8: the per-token int classes cross as their outlier twins (with_outliers); 0: as they are
 
 
 CODECS = {c.name: c for c in [
@@ -186,6 +212,8 @@ def with_native_wire(spec: CodecSpec, name: str) -> CodecSpec:
         raise ValueError(f"native_wire {name!r} is not combined with 6-bit MX rows (mx_elem)")
     if name != "native" and spec.mx_rot:
         raise ValueError(f"native_wire {name!r} is not combined with rotated MX rows (mx_rot)")
+    if name != "native" and spec.outliers:
+        raise ValueError(f"native_wire {name!r} is not combined with outlier rows (outliers)")
     return spec if spec.native_wire == NATIVE_WIRES[name] else replace(spec, native_wire=NATIVE_WIRES[name])
 
 
@@ -201,6 +229,8 @@ def with_mx_elem(spec: CodecSpec, name: str) -> CodecSpec:
             raise ValueError(f"codec {spec.name} has no MXFP4 rows: mx_elem {name!r} has nothing to apply to")
         if spec.native_wire != NATIVE:
             raise ValueError(f"mx_elem {name!r} is not combined with a 16-bit native wire (native_wire)")
+        if spec.outliers:
+            raise ValueError(f"mx_elem {name!r} is not combined with outlier rows (outliers)")
     return spec if spec.mx_elem == MX_ELEMS[name] else replace(spec, mx_elem=MX_ELEMS[name])
 
 
@@ -220,7 +250,26 @@ def with_mx_rot(spec: CodecSpec, name: str) -> CodecSpec:
             raise ValueError(f"codec {spec.name} has no MX rows: mx_rot {name!r} has nothing to apply to")
         if spec.native_wire != NATIVE:
             raise ValueError(f"mx_rot {name!r} is not combined with a 16-bit native wire (native_wire)")
+        if spec.outliers:
+            raise ValueError(f"mx_rot {name!r} is not combined with outlier rows (outliers)")
     return spec if spec.mx_rot == MX_ROTS[name] else replace(spec, mx_rot=MX_ROTS[name])
+
+
+def with_outliers(spec: CodecSpec, name: str) -> CodecSpec:
+    """The codec with the 8 largest channels of every per-token int row kept exact beside the row: "none" (the spec
+    itself) | "top8" (module docstring).  For SC_TOKEN codecs with an FMT_INT8 / FMT_INT4 / FMT_INT2 class and no
+    head-group rows; not combined with a 16-bit native wire, a 6-bit MX element type or rotated MX rows."""
+    from dataclasses import replace
+    if name not in OUTLIERS:
+        raise ValueError(f"outliers must be one of {tuple(OUTLIERS)}, got {name!r}")
+    if name != "none":
+        if spec.scale_mode != SC_TOKEN or not (spec.hi_fmt in OUT_TWIN or spec.lo_fmt in OUT_TWIN):
+            raise ValueError(f"codec {spec.name} has no per-token int rows: outliers {name!r} has nothing to apply to")
+        if needs_plan(spec):
+            raise ValueError(f"outliers {name!r} is not for codecs with head-group rows ({spec.name})")
+        if spec.native_wire != NATIVE or spec.mx_elem != FMT_MXFP4 or spec.mx_rot:
+            raise ValueError(f"outliers {name!r} is not combined with a 16-bit native wire, mx_elem or mx_rot")
+    return spec if spec.outliers == OUTLIERS[name] else replace(spec, outliers=OUTLIERS[name])
 
 
 def get_codec(name: str) -> CodecSpec:
@@ -294,10 +343,12 @@ def num_lo(spec: CodecSpec, ratio: float, S: int) -> int:
 
 
 def _resolve(fmt: int, spec: CodecSpec, native: int) -> int:
-    """A class's row format on the wire: the spec's, with its modifiers (native wire, MX element type, MX rotation)
-    applied."""
+    """A class's row format on the wire: the spec's, with its modifiers (native wire, MX element type, MX rotation,
+    outliers) applied."""
     if fmt == NATIVE:
         return native
+    if spec.outliers:
+        return OUT_TWIN.get(fmt, fmt)
     fmt = spec.mx_elem if fmt == FMT_MXFP4 else fmt
     return MX_ROT_TWIN.get(fmt, fmt) if spec.mx_rot else fmt
 
@@ -725,6 +776,37 @@ def _int_rows(fmt: int, per_byte: int) -> RowFormat:
     return RowFormat(lambda H, plan: H // per_byte, False, pack, unpack)
 
 
+def _top8(rows: torch.Tensor):
+    """The outliers of fp32 rows [n, H]: (channels [n, 8] int64, values [n, 8] fp32, the rows with those channels +0).
+    One topk over the unique keys abs_bits << 32 | (2^32 - 1 - channel): descending magnitude on the bit pattern of
+    |x| (NaN > Inf > finite), ties to the lower channel (csrc/codec.hip out_extract)."""
+    n, H = rows.shape
+    ab = rows.contiguous().view(torch.int32).to(torch.int64) & 0x7FFFFFFF
+    idx = torch.topk((ab << 32) | (0xFFFFFFFF - torch.arange(H, dtype=torch.int64)), OUT_K, dim=1).indices
+    return idx, rows.gather(1, idx), rows.scatter(1, idx, 0.0)
+
+
+def _out_rows(fmt: int, per_byte: int) -> RowFormat:
+    """The outlier twin of int format ``fmt``: [fmt's codes of the rest][8 fp32 values][8 uint16 channels]; the row's
+    scale (c.scale_row: max|rest| / qmax, _encode_cpu) is in the message's scale section as for ``fmt``."""
+    def pack(rows, c):
+        idx, val, rest = _top8(rows)
+        codes = _pack_rows(_qcodes(rest, c.spec, c.is_lo, c.scale_row, c.ch_scale), fmt).reshape(len(rows), -1)
+        return torch.cat([codes, val.contiguous().view(torch.uint8).reshape(len(rows), -1),
+                          idx.to(torch.int16).view(torch.uint8).reshape(len(rows), -1)], 1).reshape(-1)
+
+    def unpack(raw, n, c):
+        r, nc = raw.reshape(n, -1), c.H // per_byte
+        out = _dequant(_unpack_rows(r[:, :nc].reshape(-1), fmt, n, c.H), c.spec, c.is_lo, c.scale_row, c.ch_scale)
+        val = r[:, nc:nc + 4 * OUT_K].contiguous().view(torch.float32)
+        idx = r[:, nc + 4 * OUT_K:].contiguous().view(torch.int16).to(torch.int64) & 0xFFFF
+        for p in range(OUT_K):          # in pair order: of two pairs naming one channel the last holds
+            out[torch.arange(n), idx[:, p].clamp(max=c.H - 1)] = val[:, p]
+        out[(idx >= c.H).any(1)] = float("nan")
+        return out
+    return RowFormat(lambda H, plan: H // per_byte + OUT_TAIL, False, pack, unpack)
+
+
 def _mx_rows(fmt: int, code_bits: int, rot: bool = False) -> RowFormat:    # codes, then one E8M0 byte per 32 channels
     """``rot``: the rotated twin - the same bytes of the blocks rotated before the pack and back after the unpack."""
     if rot:
@@ -747,6 +829,7 @@ ROW_FORMATS = {
     FMT_F32: RowFormat(lambda H, plan: 4 * H, True, lambda rows, c: _bytes(rows),
                        lambda raw, n, c: raw.view(torch.float32).reshape(n, c.H)),
     FMT_INT8: _int_rows(FMT_INT8, 1), FMT_INT4: _int_rows(FMT_INT4, 2), FMT_INT2: _int_rows(FMT_INT2, 4),
+    FMT_INT8O: _out_rows(FMT_INT8, 1), FMT_INT4O: _out_rows(FMT_INT4, 2), FMT_INT2O: _out_rows(FMT_INT2, 4),
     FMT_MXFP4: _mx_rows(FMT_MXFP4, 4), FMT_MXFP8: _mx_rows(FMT_MXFP8, 8),
     FMT_MXFP6: _mx_rows(FMT_MXFP6, 6), FMT_MXBF6: _mx_rows(FMT_MXBF6, 6),
     FMT_MXFP4R: _mx_rows(FMT_MXFP4, 4, True), FMT_MXFP8R: _mx_rows(FMT_MXFP8, 8, True),
@@ -760,9 +843,9 @@ ROW_FORMATS = {
 
 
 def _fmt_word(spec: CodecSpec, L: Layout) -> int:
-    """Header word 7: the hi-row format; with 6-bit or rotated MX rows (with_mx_elem, with_mx_rot) the lo-row format
-    too, in bits 8-15."""
-    return L.hi_fmt | L.lo_fmt << 8 if spec.mx_elem != FMT_MXFP4 or spec.mx_rot else L.hi_fmt
+    """Header word 7: the hi-row format; with 6-bit or rotated MX rows or outlier rows (with_mx_elem, with_mx_rot,
+    with_outliers) the lo-row format too, in bits 8-15."""
+    return L.hi_fmt | L.lo_fmt << 8 if spec.mx_elem != FMT_MXFP4 or spec.mx_rot or spec.outliers else L.hi_fmt
 
 
 def _header(spec: CodecSpec, L: Layout) -> torch.Tensor:
@@ -821,8 +904,9 @@ def _encode_cpu(x, spec, L, lo_mask):
     if spec.scale_mode == SC_TOKEN:
         scales = torch.zeros(B, S)
         for is_lo, fmt, qmax in ((False, L.hi_fmt, spec.qmax_hi), (True, L.lo_fmt, spec.qmax_lo)):
-            if not ROW_FORMATS[fmt].self_scaled:
-                scales = torch.where(lo_mask if is_lo else ~lo_mask, xf.abs().amax(-1) / float(qmax), scales)
+            if not ROW_FORMATS[fmt].self_scaled:   # an outlier row: the max-abs of what its 8 outliers leave
+                am = (_top8(xf.reshape(B * S, H))[2].reshape(B, S, H) if fmt in OUT_TWIN.values() else xf).abs().amax(-1)
+                scales = torch.where(lo_mask if is_lo else ~lo_mask, am / float(qmax), scales)
     elif spec.scale_mode == SC_WINDOW:
         scales = torch.where(lo_mask[..., None], xf.abs(), torch.zeros_like(xf)).amax(dim=(1, 2))
     elif spec.scale_mode == SC_CHANNEL:
@@ -999,6 +1083,7 @@ def fork_supported(spec: CodecSpec, selection: str = "ratio") -> bool:
     int8_token_keep, mixed_int4_int8, mixed_int2_int8).  Everything else keeps the per-variant ``fake_quant``."""
     uses_kvar(spec, selection)       # an unknown selection: ValueError
     return (selection == "ratio" and spec.native_wire == NATIVE and spec.mx_elem == FMT_MXFP4 and not spec.mx_rot
+            and not spec.outliers
             and spec.scale_mode in (SC_TOKEN, SC_WINDOW)
             and (spec.hi_fmt, spec.qmax_hi) in _FORK_ROWS and (spec.lo_fmt, spec.qmax_lo) in _FORK_ROWS)
 

@@ -54,6 +54,8 @@ class Params:
                                              # rows, 6.25 bits per element; codec/wire.py with_mx_elem)
     mx_rot: str = "none"                     # "h32": a codec's MX rows quantize the 32-point Hadamard transform of
                                              # every block (codec/wire.py with_mx_rot); "none": the blocks themselves
+    outliers: str = "none"                   # "top8": a per-token int codec sends the 8 largest channels of every int
+                                             # row exactly beside the row (codec/wire.py with_outliers); "none": not
     sweep_fork: bool = False                 # sweeps: all (method, ratio) variants of a boundary layer from one
                                              # codec.fake_quant_fork pass (bit-identical to the per-variant path)
     lrp_engine: str = "auto"                 # relevance pass: "auto" (HIP engine on a GPU, autograd on the CPU) |
@@ -120,6 +122,11 @@ class Params:
             spec = wire.CODECS.get(self.codec) or wire.CODECS["passthrough"]
             wire.with_mx_rot(wire.with_mx_elem(wire.with_native_wire(spec, self.native_wire), self.mx_elem),
                              self.mx_rot)
+        if self.outliers != "none":
+            from .codec import wire   # a name no codec knows, a codec without per-token int rows, another modifier on
+            spec = wire.CODECS.get(self.codec) or wire.CODECS["passthrough"]
+            spec = wire.with_mx_elem(wire.with_native_wire(spec, self.native_wire), self.mx_elem)
+            wire.with_outliers(wire.with_mx_rot(spec, self.mx_rot), self.outliers)
 
 
 def resolve_device(p: Params) -> str:
