@@ -21,7 +21,8 @@
 enum { FMT_BF16 = 0, FMT_INT8 = 1, FMT_INT4 = 2, FMT_INT2 = 3, FMT_F32 = 4, FMT_MXFP4 = 5, FMT_MXFP8 = 6, FMT_GRP = 7,
        FMT_GRPR = 8, FMT_F16 = 9, FMT_F16S = 10, FMT_MXFP6 = 11, FMT_MXBF6 = 12,
        FMT_MXFP4R = 13, FMT_MXFP8R = 14, FMT_MXFP6R = 15, FMT_MXBF6R = 16,
-       FMT_INT8O = 17, FMT_INT4O = 18, FMT_INT2O = 19 };
+       FMT_INT8O = 17, FMT_INT4O = 18, FMT_INT2O = 19,
+       FMT_INT8R = 20, FMT_INT4R = 21, FMT_INT2R = 22 };
 // Outlier rows (FMT_INT8O / FMT_INT4O / FMT_INT2O; codec/wire.py with_outliers resolves the int classes of a per-token
 // codec to them): [the plain twin's code bytes][8 fp32 values][8 uint16 channels], the twin's bytes + OUT_TAIL.  The 8
 // channels with the largest abs_bits(x) (NaN > Inf > finite; ties to the lower channel), listed in that order, cross
@@ -39,6 +40,30 @@ template <bool OUT>
 __device__ __forceinline__ int out_twin(int fmt) {   // an outlier row's plain twin, any other format itself
   if constexpr (OUT) {
     if (is_out_fmt(fmt)) return fmt - (FMT_INT8O - FMT_INT8);
+  }
+  return fmt;
+}
+// Rotated per-token int rows (FMT_INT8R / FMT_INT4R / FMT_INT2R; codec/wire.py with_row_rot resolves the int classes of
+// a per-token codec to them): the bytes of the plain twin - its codes, the scale in the message's scale section - but
+// codes and scale describe y = H128 x / 8 of every 128-channel block, H128 the natural-order Sylvester matrix: one
+// massive channel is spread over its block, whose max|y| - and with it the row's one step - falls by up to 8 (QuaRot /
+// SpinQuant, block-diagonal: 896 = 7 * 128).  Encode: seven fp32 butterfly stages (a, b) -> (a + b, a - b) at channel
+// strides 1, 2, 4, 8, 16, 32, 64 in that order, the lower index keeping the sum, one multiply by 0.125f, then the plain
+// row's path unchanged (max-abs on bit patterns, tok_scale, tok_inv, tok_code).  Decode: the integer codes as floats,
+// the same seven stages (|sum| <= 128 * 127: exact), one multiply by s * 0.0625f (H128 H128 = 128 I = 8 * 16 I).  No add
+// follows a multiply on either side, so there is nothing for fp contraction to fuse and the CPU oracle (codec/wire.py
+// _wht128) agrees bit for bit.  The unit is the token row: a NaN / Inf in any block, or a finite row whose butterflies
+// overflow (max-abs from about 2^120 up), makes y - so the row's scale, so the whole decoded row - non-finite: loud,
+// never clipped.  Where the stages run: wht_row16.  Messages with such rows run the RR instantiations of pack_kernel /
+// unpack_kernel (every rotated branch under `if constexpr (RR)`; SC_TOKEN and H % 128 == 0 only, not next to
+// head-group, 16-bit, 6-bit, rotated MX or outlier rows), so the instantiations every other codec runs keep their
+// instruction stream.  Header word 7 is hi_fmt | lo_fmt << 8 and unpack_kernel<RR> decodes a message that says
+// otherwise to NaN.
+__device__ __forceinline__ bool is_rr_fmt(int fmt) { return fmt >= FMT_INT8R && fmt <= FMT_INT2R; }
+template <bool RR>
+__device__ __forceinline__ int rr_twin(int fmt) {   // a rotated int row's plain twin, any other format itself
+  if constexpr (RR) {
+    if (is_rr_fmt(fmt)) return fmt - (FMT_INT8R - FMT_INT8);
   }
   return fmt;
 }
@@ -134,8 +159,11 @@ struct CodecArgs {
   int grp_code_bytes;           // FMT_GRP / FMT_GRPR: sum over groups of 8 b_g (row = codes + 4 G scale bytes)
 };
 
-template <bool W16, bool MX6, bool MXR = false, bool OUT = false>
+template <bool W16, bool MX6, bool MXR = false, bool OUT = false, bool RR = false>
 __device__ __forceinline__ int fmt_row_bytes(int fmt, int H) {
+  if constexpr (RR) {    // a rotated int row has the bytes of its plain twin
+    if (is_rr_fmt(fmt)) return fmt == FMT_INT8R ? H : fmt == FMT_INT4R ? H / 2 : H / 4;
+  }
   if constexpr (OUT) {   // an outlier row has the bytes of its plain twin and the tail
     if (is_out_fmt(fmt)) return (fmt == FMT_INT8O ? H : fmt == FMT_INT4O ? H / 2 : H / 4) + OUT_TAIL;
   }
@@ -156,12 +184,12 @@ __device__ __forceinline__ int fmt_row_bytes(int fmt, int H) {
   return fmt == FMT_F32 ? 4 * H : fmt == FMT_BF16 ? 2 * H : fmt == FMT_INT8 ? H : fmt == FMT_INT4 ? H / 2 :
          fmt == FMT_MXFP4 ? H / 2 + H / 32 : fmt == FMT_MXFP8 ? H + H / 32 : H / 4;
 }
-template <bool ROT, bool W16, bool MX6, bool MXR = false, bool OUT = false>
+template <bool ROT, bool W16, bool MX6, bool MXR = false, bool OUT = false, bool RR = false>
 __device__ __forceinline__ int row_bytes(const CodecArgs& a, int fmt) {
   if constexpr (ROT) {
     if (fmt == FMT_GRPR) return a.grp_code_bytes + 4 * (a.H / 64);
   }
-  return fmt == FMT_GRP ? a.grp_code_bytes + 4 * (a.H / 64) : fmt_row_bytes<W16, MX6, MXR, OUT>(fmt, a.H);
+  return fmt == FMT_GRP ? a.grp_code_bytes + 4 * (a.H / 64) : fmt_row_bytes<W16, MX6, MXR, OUT, RR>(fmt, a.H);
 }
 // Formats whose rows carry their own scales (or none): no entry in the message's scale section.  A macro, and the
 // rotated format joined with `|`: the compiler simplifies the body of an inlined function on its own first, and the
@@ -331,19 +359,20 @@ __device__ __forceinline__ void kvar_prefix(const CodecArgs& a, int b, int& Kb, 
 // among the class's rows of its window (lo_prefix), the class's rows of the windows before (b k / b (S - k) for fixed
 // k, the k vector's prefix sum for variable k, whose hi section starts right after the Sum k lo rows).
 struct RowSlot { uint8_t* p; int fmt, qmax, b; };
-template <bool ROT, bool W16, bool MX6, bool MXR = false, bool OUT = false>
+template <bool ROT, bool W16, bool MX6, bool MXR = false, bool OUT = false, bool RR = false>
 __device__ __forceinline__ RowSlot row_slot(const CodecArgs& a, int row) {
   const int b = row / a.S, j = row - b * a.S;
   const uint32_t* mask = (const uint32_t*)(a.msg + a.off_mask) + (size_t)b * a.mw;
   bool is_lo;
   const int slot_lo = lo_prefix(mask, a.mw, j, is_lo);
   const int fmt = is_lo ? a.lo_fmt : a.hi_fmt;
-  const int rb = row_bytes<ROT, W16, MX6, MXR, OUT>(a, fmt);
+  const int rb = row_bytes<ROT, W16, MX6, MXR, OUT, RR>(a, fmt);
   uint8_t* p;
   if (a.off_kvec >= 0) {
     int Kb, Kt;
     kvar_prefix(a, b, Kb, Kt);
-    const long long off_hi = a.off_lo + (((long long)Kt * row_bytes<ROT, W16, MX6, MXR, OUT>(a, a.lo_fmt) + 15) & ~15ll);
+    const long long off_hi = a.off_lo + (((long long)Kt * row_bytes<ROT, W16, MX6, MXR, OUT, RR>(a, a.lo_fmt) + 15) &
+                                       ~15ll);
     p = is_lo ? a.msg + a.off_lo + ((size_t)Kb + slot_lo) * rb
               : a.msg + off_hi + ((size_t)b * a.S - Kb + (j - slot_lo)) * rb;
   } else {
@@ -575,6 +604,34 @@ __device__ __forceinline__ void mx_unpack8_rot(const uint8_t* __restrict__ row, 
   wht_quad(o);
 #pragma unroll
   for (int e = 0; e < 8; ++e) o[e] *= 0.125f;
+}
+
+// Rotated per-token int rows: the unnormalised 128-point Walsh-Hadamard transform of a block held 8 consecutive
+// channels per lane by the 16 lanes of one DPP row (col = (64 c + lane) 8: block = lane >> 4 of its chunk), in place.
+// Strides 1, 2, 4 are wht8 on the lane's own values, strides 8 and 16 wht_quad (lanes ^1 and ^2), strides 32 and 64 pair
+// lanes ^4 and ^8 by the row controls of the same DPP operand path (quad_mov is one DPP move under any control):
+// lane ^ 8 is a rotation of the 16-lane row by 8 (row_ror:8), lane ^ 4 the reversal of the row's 8-lane halves
+// (row_half_mirror: lane ^ 7) followed by the reversal of the quads (quad_perm [3, 2, 1, 0]: lane ^ 3).  wht_quad's sign
+// convention: the lane with the stride bit set flips its own sign bit, and both add the partner's value.  Five DPP
+// moves, four xors and four adds per value on top of wht8 - no LDS, no ds_bpermute_b32, no scratch.
+// Every lane of a DPP row must be at the moves (a disabled source lane yields 0): H % 128 == 0 makes the col >= H
+// early-out drop whole 16-lane rows, and a row's format is wave-uniform (row_slot).
+enum { DPP_QUAD_REV = 0x1B, DPP_ROW_ROR8 = 0x128, DPP_ROW_HALF_MIRROR = 0x141 };
+__device__ __forceinline__ void wht_row16(float (&v)[8]) {
+  const uint32_t lane = threadIdx.x & 63;
+  const uint32_t s4 = (lane & 4u) << 29, s8 = (lane & 8u) << 28;
+  wht8(v);
+  wht_quad(v);
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    const uint32_t u = __float_as_uint(v[e]);
+    v[e] = __uint_as_float(quad_mov<DPP_QUAD_REV>(quad_mov<DPP_ROW_HALF_MIRROR>(u))) + __uint_as_float(u ^ s4);
+  }
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    const uint32_t u = __float_as_uint(v[e]);
+    v[e] = __uint_as_float(quad_mov<DPP_ROW_ROR8>(u)) + __uint_as_float(u ^ s8);
+  }
 }
 
 // FMT_GRP: the 8 lanes holding channels [64 g, 64 g + 64) of a row (8 values each) quantize their group.
@@ -1022,18 +1079,30 @@ __device__ __forceinline__ void out_patch(float (&o)[8], const OutPairs& p, int 
   if (p.bad) fill8(o, __builtin_nanf(""));
 }
 
-template <int NCH, class T, bool ROT = false, bool W16 = false, bool MX6 = false, bool MXR = false, bool OUT = false>
+template <int NCH, class T, bool ROT = false, bool W16 = false, bool MX6 = false, bool MXR = false, bool OUT = false,
+          bool RR = false>
 __global__ __launch_bounds__(256) void pack_kernel(CodecArgs a) {
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= a.B * a.S) return;
   const int lane = threadIdx.x & 63;
-  const RowSlot rs = row_slot<ROT, W16, MX6, MXR, OUT>(a, row);
+  const RowSlot rs = row_slot<ROT, W16, MX6, MXR, OUT, RR>(a, row);
   uint8_t* dst = rs.p;
   const bool orow = OUT && is_out_fmt(rs.fmt);   // an outlier row: fmt is its plain twin's
-  const int fmt = out_twin<OUT>(rs.fmt), qmax = rs.qmax, b = rs.b;
+  const bool rrow = RR && is_rr_fmt(rs.fmt);     // a rotated int row: fmt is its plain twin's
+  const int fmt = rr_twin<RR>(out_twin<OUT>(rs.fmt)), qmax = rs.qmax, b = rs.b;
   float v[NCH][8];
   load_row8<NCH>((const T*)a.x + (size_t)row * a.H, a.H, v);
   float* scales = (float*)(a.msg + a.off_scale);
+  if constexpr (RR) {   // a rotated int row: v becomes y = H128 x / 8, all 64 lanes and all chunks at the moves (chunks
+    if (rrow) {         // past H rotate zeros to zeros); from here on the row is its plain twin's
+#pragma unroll
+      for (int c = 0; c < NCH; ++c) {
+        wht_row16(v[c]);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) v[c][e] *= 0.125f;
+      }
+    }
+  }
 
   // scale / quantiser for this row
   float inv = 0.f, mul = 0.f;  // code = round(x * inv) for token & channel; window mode uses ref formula
@@ -1226,15 +1295,17 @@ __device__ __forceinline__ void mx6_unpack_row(const uint8_t* __restrict__ row, 
   }
 }
 
-template <int NCH, class T, bool ROT = false, bool W16 = false, bool MX6 = false, bool MXR = false, bool OUT = false>
+template <int NCH, class T, bool ROT = false, bool W16 = false, bool MX6 = false, bool MXR = false, bool OUT = false,
+          bool RR = false>
 __global__ __launch_bounds__(256) void unpack_kernel(CodecArgs a) {
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= a.B * a.S) return;
   const int lane = threadIdx.x & 63;
-  const RowSlot rs = row_slot<ROT, W16, MX6, MXR, OUT>(a, row);
+  const RowSlot rs = row_slot<ROT, W16, MX6, MXR, OUT, RR>(a, row);
   const uint8_t* src = rs.p;
   const bool orow = OUT && is_out_fmt(rs.fmt);   // an outlier row: fmt is its plain twin's
-  const int fmt = out_twin<OUT>(rs.fmt), qmax = rs.qmax, b = rs.b;
+  const bool rrow = RR && is_rr_fmt(rs.fmt);     // a rotated int row: fmt is its plain twin's
+  const int fmt = rr_twin<RR>(out_twin<OUT>(rs.fmt)), qmax = rs.qmax, b = rs.b;
   const float* scales = (const float*)(a.msg + a.off_scale);
   float s = 0.f;
   if (!SELF_SCALED(ROT, W16, MX6, MXR, fmt)) {
@@ -1242,8 +1313,8 @@ __global__ __launch_bounds__(256) void unpack_kernel(CodecArgs a) {
     else if (a.scale_mode == SC_WINDOW) s = scales[b];
   }
   T* out = (T*)a.x + (size_t)row * a.H;
-  if constexpr (MX6 || MXR || OUT) {
-    // header word 7 of a message with 6-bit, rotated MX or outlier rows names both classes' formats; one that disagrees with the
+  if constexpr (MX6 || MXR || OUT || RR) {
+    // header word 7 of a message with 6-bit, rotated or outlier rows names both classes' formats; one that disagrees with the
     // formats this launch was given (encoded with another element type, or without the modifier) decodes to NaN - loud
     if (((const int*)a.msg)[7] != (a.hi_fmt | a.lo_fmt << 8)) {
       float o[8];
@@ -1350,6 +1421,18 @@ __global__ __launch_bounds__(256) void unpack_kernel(CodecArgs a) {
       for (int e = 0; e < 8; ++e) q[e] = ((int)(w << (30 - 2 * e))) >> 30;
     }
     float o[8];
+    if constexpr (RR) {   // x' = H128 q (s / 16); the 16 lanes of the block's DPP row are here (wht_row16)
+      if (rrow) {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) o[e] = (float)q[e];
+        wht_row16(o);
+        const float sc = s * 0.0625f;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) o[e] *= sc;
+        store8(out + col, o);
+        continue;
+      }
+    }
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
       const float qf = (float)q[e];
@@ -1694,10 +1777,11 @@ EDGE_API int edge_rowmax(const float* in, float* out, int R, int H, hipStream_t 
 // A message with FMT_GRPR rows goes to the ROT instantiations (which handle every other format too).
 static bool has_fmt(int hi_fmt, int lo_fmt, int fmt) { return hi_fmt == fmt || lo_fmt == fmt; }
 
-template <bool PACK, int NCH, class T, bool ROT, bool W16 = false, bool MX6 = false, bool MXR = false, bool OUT = false>
+template <bool PACK, int NCH, class T, bool ROT, bool W16 = false, bool MX6 = false, bool MXR = false, bool OUT = false,
+          bool RR = false>
 static void launch_codec(dim3 grid, hipStream_t st, const CodecArgs& a) {
-  if constexpr (PACK) hipLaunchKernelGGL((pack_kernel<NCH, T, ROT, W16, MX6, MXR, OUT>), grid, dim3(256), 0, st, a);
-  else hipLaunchKernelGGL((unpack_kernel<NCH, T, ROT, W16, MX6, MXR, OUT>), grid, dim3(256), 0, st, a);
+  if constexpr (PACK) hipLaunchKernelGGL((pack_kernel<NCH, T, ROT, W16, MX6, MXR, OUT, RR>), grid, dim3(256), 0, st, a);
+  else hipLaunchKernelGGL((unpack_kernel<NCH, T, ROT, W16, MX6, MXR, OUT, RR>), grid, dim3(256), 0, st, a);
 }
 
 // edge_pack / edge_unpack: argument checks, CodecArgs and the (ROT | W16 | plain) x activation dtype x NCH dispatch.
@@ -1706,7 +1790,9 @@ static void launch_codec(dim3 grid, hipStream_t st, const CodecArgs& a) {
 // to the MX6 instantiations; together with FMT_GRPR, FMT_F16 or FMT_F16S rows it is rejected the same way.  A message
 // with rotated MX rows goes to the MXR instantiations - MXR x MX6 when one of them is 6-bit - under the same rejections.
 // A message with outlier rows goes to the OUT instantiations; with any scale mode but SC_TOKEN, or next to head-group,
-// 16-bit, 6-bit or rotated rows, it is rejected before anything is launched.
+// 16-bit, 6-bit or rotated rows, it is rejected before anything is launched.  A message with rotated int rows goes to the
+// RR instantiations; with H % 128 != 0, any scale mode but SC_TOKEN, or next to head-group, 16-bit, 6-bit, rotated MX or
+// outlier rows, it is rejected the same way.
 template <bool PACK>
 static int run_codec(void* x, void* msg, long long om, long long os, long long oh, long long ol, long long okv,
                      long long opl, int B, int S, int H, int k, int hi_fmt, int lo_fmt, int scale_mode, int qmax_hi,
@@ -1719,8 +1805,12 @@ static int run_codec(void* x, void* msg, long long om, long long os, long long o
   const bool mx6 = mxr6 || has_fmt(hi_fmt, lo_fmt, FMT_MXFP6) || has_fmt(hi_fmt, lo_fmt, FMT_MXBF6);
   const bool out = has_fmt(hi_fmt, lo_fmt, FMT_INT8O) || has_fmt(hi_fmt, lo_fmt, FMT_INT4O) ||
                    has_fmt(hi_fmt, lo_fmt, FMT_INT2O);
+  const bool rr = has_fmt(hi_fmt, lo_fmt, FMT_INT8R) || has_fmt(hi_fmt, lo_fmt, FMT_INT4R) ||
+                  has_fmt(hi_fmt, lo_fmt, FMT_INT2R);
   if ((rot && w16) || ((mx6 || mxr) && (rot || w16))) return (int)hipErrorInvalidValue;
   if (out && (rot || w16 || mx6 || mxr || has_fmt(hi_fmt, lo_fmt, FMT_GRP) || scale_mode != SC_TOKEN))
+    return (int)hipErrorInvalidValue;
+  if (rr && (out || rot || w16 || mx6 || mxr || has_fmt(hi_fmt, lo_fmt, FMT_GRP) || scale_mode != SC_TOKEN || H % 128))
     return (int)hipErrorInvalidValue;
   if ((rot || has_fmt(hi_fmt, lo_fmt, FMT_GRP)) && (H % 64 || opl < 0 || grp_code_bytes <= 0))
     return (int)hipErrorInvalidValue;
@@ -1746,6 +1836,9 @@ static int run_codec(void* x, void* msg, long long om, long long os, long long o
   else if (mx6) DISPATCH_NCH(H, (launch_codec<PACK, NCH, bf16_t, false, false, true>(grid, st, a)));
   else if (out && x_f32) DISPATCH_NCH(H, (launch_codec<PACK, NCH, float, false, false, false, false, true>(grid, st, a)));
   else if (out) DISPATCH_NCH(H, (launch_codec<PACK, NCH, bf16_t, false, false, false, false, true>(grid, st, a)));
+  else if (rr && x_f32)
+    DISPATCH_NCH(H, (launch_codec<PACK, NCH, float, false, false, false, false, false, true>(grid, st, a)));
+  else if (rr) DISPATCH_NCH(H, (launch_codec<PACK, NCH, bf16_t, false, false, false, false, false, true>(grid, st, a)));
   else if (x_f32) DISPATCH_NCH(H, (launch_codec<PACK, NCH, float, false>(grid, st, a)));
   else DISPATCH_NCH(H, (launch_codec<PACK, NCH, bf16_t, false>(grid, st, a)));
   return (int)hipGetLastError();

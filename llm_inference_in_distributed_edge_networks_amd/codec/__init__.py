@@ -32,6 +32,8 @@ mxfp4_keep             native dtype    MXFP4           E8M0 / 32ch  Q1 with MX b
                        rotated twins of the same element type       32-channel block (Hadamard, quad DPP moves)
 (the int rows above)   with_outliers "top8": the int8 / int4 /      the row's 8 largest channels cross as exact
                        int2 rows of the per-token codecs            fp32 beside it; the scale is the rest's
+(the int rows above)   with_row_rot "h128": the same rows as        the plain rows' bytes of y = H128 x / 8 per
+                       their rotated twins (H % 128 == 0)           128-channel block (Hadamard, DPP row moves)
 rgroup                 head groups     --              per group    every 64-channel group (one head) its
                                                                     own max-abs scale and 2/4/8-bit width
 mixed_rgroup_int8      int8            head groups     token/group  config 5 (relevance-allocated widths
@@ -73,6 +75,13 @@ channels after the row's codes (48 bytes a row), and the row's scale is the max-
 loud channel no longer rounds the rest of an int4 / int2 row to zero.  For ``int4_token``, ``int8_token``,
 ``mixed_int4_int8``, ``mixed_int2_int8`` and ``int8_token_keep``; not combined with the other modifiers.
 
+``with_row_rot(spec, "h128")`` (params key ``row_rot``) is the other remedy for the same rows and codecs (QuaRot /
+SpinQuant): every 128-channel block of a per-token int row is quantized in the basis of the orthonormal 128-point
+Hadamard transform, at the plain row's bytes (896 = 7 x 128; the hidden size must be a multiple of 128).  A loud
+channel is spread over its block, so the row's max-abs and step fall by up to 8.  It pays where the spread spike stays
+within a few steps of the other channels - int8 rows, moderate spikes at int4; at 2 bits and for very large spikes at
+4 bits it can lose, and ``with_outliers`` is the remedy there.  Not combined with the other modifiers.
+
 ``fake_quant_fork(x, spec, B, S, variants, importances)`` is ``fake_quant`` for a whole list of (importance source, k)
 variants of one codec at once - the sweep's step between the shared prefix and the stacked suffix: one sort per
 source, one read of ``x``, one write per variant, bit-identical to the per-variant round trip (``fork_supported``: the
@@ -83,8 +92,9 @@ window (ascending importance, ties broken by position) are the lo class.
 """
 from . import plan  # noqa: F401  (codec.plan: the head-group bit plans)
 from .wire import (CODECS, CodecSpec, Layout, decode, encode, fake_quant, fake_quant_fork, fork_supported, get_codec,
-                   layout, message_bytes, select_mask, with_mx_elem, with_mx_rot, with_native_wire, with_outliers)
+                   layout, message_bytes, select_mask, with_mx_elem, with_mx_rot, with_native_wire, with_outliers,
+                   with_row_rot)
 
 __all__ = ["CODECS", "CodecSpec", "Layout", "decode", "encode", "fake_quant", "fake_quant_fork", "fork_supported",
            "get_codec", "layout", "message_bytes", "select_mask", "with_mx_elem", "with_mx_rot",
-           "with_native_wire", "with_outliers"]
+           "with_native_wire", "with_outliers", "with_row_rot"]

@@ -85,6 +85,23 @@ Header word 7 is ``hi_fmt | lo_fmt << 8``.  Not for per-window / per-channel sca
 reference's Q1 bit for bit), not for codecs with head-group rows, not combined with a 16-bit native wire, ``mx_elem``
 or ``mx_rot``; such specs are not served by ``fake_quant_fork``.
 
+Rotated per-token int rows.  ``with_row_rot(spec, "h128")`` - a modifier too - resolves every ``FMT_INT8`` / ``FMT_INT4``
+/ ``FMT_INT2`` class of the same per-token codecs to its rotated twin (``FMT_INT8R`` = 20, ``FMT_INT4R`` = 21,
+``FMT_INT2R`` = 22), the QuaRot / SpinQuant remedy for the same massive channels: the plain row's bytes (its codes; the
+per-token scale in the message's scale section), but codes and scale describe ``y = H128 x / 8`` of every 128-channel
+block, H128 the natural-order Sylvester matrix as H32 above - block-diagonal, so it needs ``H % 128 == 0`` (896 = 7 x
+128; ``layout`` raises otherwise), and a loud channel is spread over its block: the row's max-abs, and with it its one
+step, falls by up to 8.  Encode: seven fp32 butterfly stages ``(a, b) -> (a + b, a - b)`` at channel strides 1, 2, 4, 8,
+16, 32, 64 (the lower index keeps the sum), one multiply by 0.125, then the plain row's quantizer.  Decode: the integer
+codes as floats, the same seven stages (sums at most 128 x 127: exact), one multiply by ``s * 0.0625`` (H128 H128 = 128
+I).  No add follows a multiply on either side, so the GPU's message is the CPU's byte for byte.  The unit is the token
+row: a NaN / Inf in any block makes that block's y, hence the row's scale, hence the whole decoded row non-finite.
+Overflow of the rotation: so does a finite row whose butterflies overflow (max-abs from about 2^120 up) - loud, never
+clipped.  Header word 7 is ``hi_fmt | lo_fmt << 8``.  Rotation pays where the spread spike stays within a few steps of
+the other channels (int8; moderate spikes at int4); at 2 bits and for very large spikes at 4 bits it can lose, and
+``with_outliers`` is the remedy.  Not combined with ``native_wire``, ``mx_elem``, ``mx_rot`` or ``outliers``; such
+specs are not served by ``fake_quant_fork``.
+
 ``encode``/``decode`` run the gfx950 kernels of ``csrc/codec.hip`` for CUDA
 tensors and a bit-identical PyTorch implementation for CPU tensors.
 
@@ -116,6 +133,8 @@ MX_ROT_TWIN = {FMT_MXFP4: FMT_MXFP4R, FMT_MXFP8: FMT_MXFP8R, FMT_MXFP6: FMT_MXFP
 FMT_INT8O, FMT_INT4O, FMT_INT2O = 17, 18, 19   # per-token int rows + the row's 8 largest channels exact (with_outliers)
 OUT_TWIN = {FMT_INT8: FMT_INT8O, FMT_INT4: FMT_INT4O, FMT_INT2: FMT_INT2O}
 OUT_K, OUT_TAIL = 8, 48     # outliers of such a row; bytes of its tail: 8 fp32 values, 8 uint16 channels
+FMT_INT8R, FMT_INT4R, FMT_INT2R = 20, 21, 22   # per-token int rows of the Hadamard-rotated 128-channel blocks (with_row_rot)
+ROW_ROT_TWIN = {FMT_INT8: FMT_INT8R, FMT_INT4: FMT_INT4R, FMT_INT2: FMT_INT2R}
 GRP_FORMATS = (FMT_GRP, FMT_GRPR)
 SC_TOKEN, SC_WINDOW, SC_CHANNEL, SC_NONE = 0, 1, 2, 3
 CH_MAXABS, CH_MEAN = 0, 1
@@ -124,6 +143,7 @@ NATIVE_WIRES = {"native": NATIVE, "bf16": FMT_BF16, "fp16": FMT_F16, "fp16s": FM
 MX_ELEMS = {"fp4": FMT_MXFP4, "e2m3": FMT_MXFP6, "e3m2": FMT_MXBF6}                         # with_mx_elem
 MX_ROTS = {"none": 0, "h32": 32}                                                            # with_mx_rot: block size
 OUTLIERS = {"none": 0, "top8": OUT_K}                                                       # with_outliers: count
+ROW_ROTS = {"none": 0, "h128": 128}                                                         # with_row_rot: block size
 
 
 @dataclass(frozen=True)
@@ -143,6 +163,7 @@ class CodecSpec:
     mx_elem: int = FMT_MXFP4     # row format of the FMT_MXFP4 classes on the wire (with_mx_elem)
     mx_rot: int = 0              # 32: the MX classes cross as their rotated twins (with_mx_rot); 0: as they are
     outliers: int = 0            # 8: the per-token int classes cross as their outlier twins (with_outliers); 0: as they are
+    row_rot: int = 0             # 128: the per-token int classes cross as their rotated twins (with_row_rot); 0: as they are
 
 
 CODECS = {c.name: c for c in [
@@ -214,6 +235,8 @@ def with_native_wire(spec: CodecSpec, name: str) -> CodecSpec:
         raise ValueError(f"native_wire {name!r} is not combined with rotated MX rows (mx_rot)")
     if name != "native" and spec.outliers:
         raise ValueError(f"native_wire {name!r} is not combined with outlier rows (outliers)")
+    if name != "native" and spec.row_rot:
+        raise ValueError(f"native_wire {name!r} is not combined with rotated int rows (row_rot)")
     return spec if spec.native_wire == NATIVE_WIRES[name] else replace(spec, native_wire=NATIVE_WIRES[name])
 
 
@@ -231,6 +254,8 @@ def with_mx_elem(spec: CodecSpec, name: str) -> CodecSpec:
             raise ValueError(f"mx_elem {name!r} is not combined with a 16-bit native wire (native_wire)")
         if spec.outliers:
             raise ValueError(f"mx_elem {name!r} is not combined with outlier rows (outliers)")
+        if spec.row_rot:
+            raise ValueError(f"mx_elem {name!r} is not combined with rotated int rows (row_rot)")
     return spec if spec.mx_elem == MX_ELEMS[name] else replace(spec, mx_elem=MX_ELEMS[name])
 
 
@@ -252,6 +277,8 @@ def with_mx_rot(spec: CodecSpec, name: str) -> CodecSpec:
             raise ValueError(f"mx_rot {name!r} is not combined with a 16-bit native wire (native_wire)")
         if spec.outliers:
             raise ValueError(f"mx_rot {name!r} is not combined with outlier rows (outliers)")
+        if spec.row_rot:
+            raise ValueError(f"mx_rot {name!r} is not combined with rotated int rows (row_rot)")
     return spec if spec.mx_rot == MX_ROTS[name] else replace(spec, mx_rot=MX_ROTS[name])
 
 
@@ -269,7 +296,27 @@ def with_outliers(spec: CodecSpec, name: str) -> CodecSpec:
             raise ValueError(f"outliers {name!r} is not for codecs with head-group rows ({spec.name})")
         if spec.native_wire != NATIVE or spec.mx_elem != FMT_MXFP4 or spec.mx_rot:
             raise ValueError(f"outliers {name!r} is not combined with a 16-bit native wire, mx_elem or mx_rot")
+        if spec.row_rot:
+            raise ValueError(f"outliers {name!r} is not combined with rotated int rows (row_rot)")
     return spec if spec.outliers == OUTLIERS[name] else replace(spec, outliers=OUTLIERS[name])
+
+
+def with_row_rot(spec: CodecSpec, name: str) -> CodecSpec:
+    """The codec with its per-token int rows quantized in the basis of the 128-point Hadamard transform of every
+    128-channel block: "none" (the spec itself) | "h128" (module docstring).  For the specs ``with_outliers`` takes:
+    SC_TOKEN codecs with an FMT_INT8 / FMT_INT4 / FMT_INT2 class and no head-group rows; not combined with a 16-bit
+    native wire, a 6-bit MX element type, rotated MX rows or outlier rows."""
+    from dataclasses import replace
+    if name not in ROW_ROTS:
+        raise ValueError(f"row_rot must be one of {tuple(ROW_ROTS)}, got {name!r}")
+    if name != "none":
+        if spec.scale_mode != SC_TOKEN or not (spec.hi_fmt in ROW_ROT_TWIN or spec.lo_fmt in ROW_ROT_TWIN):
+            raise ValueError(f"codec {spec.name} has no per-token int rows: row_rot {name!r} has nothing to apply to")
+        if needs_plan(spec):
+            raise ValueError(f"row_rot {name!r} is not for codecs with head-group rows ({spec.name})")
+        if spec.native_wire != NATIVE or spec.mx_elem != FMT_MXFP4 or spec.mx_rot or spec.outliers:
+            raise ValueError(f"row_rot {name!r} is not combined with a 16-bit native wire, mx_elem, mx_rot or outliers")
+    return spec if spec.row_rot == ROW_ROTS[name] else replace(spec, row_rot=ROW_ROTS[name])
 
 
 def get_codec(name: str) -> CodecSpec:
@@ -344,11 +391,13 @@ def num_lo(spec: CodecSpec, ratio: float, S: int) -> int:
 
 def _resolve(fmt: int, spec: CodecSpec, native: int) -> int:
     """A class's row format on the wire: the spec's, with its modifiers (native wire, MX element type, MX rotation,
-    outliers) applied."""
+    outliers, row rotation) applied."""
     if fmt == NATIVE:
         return native
     if spec.outliers:
         return OUT_TWIN.get(fmt, fmt)
+    if spec.row_rot:
+        return ROW_ROT_TWIN.get(fmt, fmt)
     fmt = spec.mx_elem if fmt == FMT_MXFP4 else fmt
     return MX_ROT_TWIN.get(fmt, fmt) if spec.mx_rot else fmt
 
@@ -360,6 +409,8 @@ def layout(spec: CodecSpec, B: int, S: int, H: int, k: int, dtype: torch.dtype =
         raise ValueError("hidden size must be a multiple of 32 for the packed formats")
     nf = native_fmt(dtype) if spec.native_wire == NATIVE else spec.native_wire
     hi, lo = _resolve(spec.hi_fmt, spec, nf), _resolve(spec.lo_fmt, spec, nf)
+    if spec.row_rot and H % spec.row_rot:
+        raise ValueError(f"rotated int rows need a hidden size multiple of {spec.row_rot}")
     plan = None
     if hi in GRP_FORMATS or lo in GRP_FORMATS:
         if H % GROUP:
@@ -657,6 +708,25 @@ def _rot32(rows: torch.Tensor, scale: float) -> torch.Tensor:
     return (_wht32(rows.float().reshape(n, H // 32, 32)) * scale).reshape(n, H)
 
 
+def _wht128(v: torch.Tensor) -> torch.Tensor:
+    """Unnormalised 128-point Walsh-Hadamard transform (Sylvester order) of the last dimension in fp32: the butterflies
+    (a, b) -> (a + b, a - b) at channel strides 1, 2, 4, 8, 16, 32, 64 in that order, the lower index keeping the sum -
+    the order and operations of csrc/codec.hip wht_row16."""
+    lead = v.shape[:-1]
+    for h in (1, 2, 4, 8, 16, 32, 64):
+        p = v.reshape(*lead, 128 // (2 * h), 2, h)
+        a, b = p[..., 0, :], p[..., 1, :]
+        v = torch.stack((a + b, a - b), -2).reshape(*lead, 128)
+    return v
+
+
+def _rot128(rows: torch.Tensor, scale) -> torch.Tensor:
+    """``scale`` H128 x of every 128-channel block of fp32 rows [n, H]: 0.125 before the quantizer, the rows' s / 16
+    ([n, 1, 1]) on the decoder's integer sums (one multiply, after the last add)."""
+    n, H = rows.shape
+    return (_wht128(rows.float().reshape(n, H // 128, 128)) * scale).reshape(n, H)
+
+
 def hadamard64(x: torch.Tensor) -> torch.Tensor:
     """y_g = H64 x_g / 8 for every 64-channel group of fp32 rows [n, H]: orthonormal, symmetric, its own inverse.
     The scaling by 1/8 is exact, so the only roundings are those of the 6 butterfly levels' fp32 adds."""
@@ -767,11 +837,15 @@ class RowFormat:
     unpack: Callable[[torch.Tensor, int, RowCtx], torch.Tensor]     # (bytes, n, ctx) -> fp32 rows [n, H]
 
 
-def _int_rows(fmt: int, per_byte: int) -> RowFormat:
+def _int_rows(fmt: int, per_byte: int, rot: bool = False) -> RowFormat:
+    """``rot``: the rotated twin (SC_TOKEN only) - the same bytes of y = H128 x / 8, whose max-abs made c.scale_row
+    (_encode_cpu); the decoder rotates the integer codes back and multiplies once, by s / 16."""
     def pack(rows, c):
-        return _pack_rows(_qcodes(rows, c.spec, c.is_lo, c.scale_row, c.ch_scale), fmt)
+        return _pack_rows(_qcodes(_rot128(rows, 0.125) if rot else rows, c.spec, c.is_lo, c.scale_row, c.ch_scale), fmt)
 
     def unpack(raw, n, c):
+        if rot:
+            return _rot128(_unpack_rows(raw, fmt, n, c.H), (c.scale_row * 0.0625)[:, None, None])
         return _dequant(_unpack_rows(raw, fmt, n, c.H), c.spec, c.is_lo, c.scale_row, c.ch_scale)
     return RowFormat(lambda H, plan: H // per_byte, False, pack, unpack)
 
@@ -830,6 +904,8 @@ ROW_FORMATS = {
                        lambda raw, n, c: raw.view(torch.float32).reshape(n, c.H)),
     FMT_INT8: _int_rows(FMT_INT8, 1), FMT_INT4: _int_rows(FMT_INT4, 2), FMT_INT2: _int_rows(FMT_INT2, 4),
     FMT_INT8O: _out_rows(FMT_INT8, 1), FMT_INT4O: _out_rows(FMT_INT4, 2), FMT_INT2O: _out_rows(FMT_INT2, 4),
+    FMT_INT8R: _int_rows(FMT_INT8, 1, True), FMT_INT4R: _int_rows(FMT_INT4, 2, True),
+    FMT_INT2R: _int_rows(FMT_INT2, 4, True),
     FMT_MXFP4: _mx_rows(FMT_MXFP4, 4), FMT_MXFP8: _mx_rows(FMT_MXFP8, 8),
     FMT_MXFP6: _mx_rows(FMT_MXFP6, 6), FMT_MXBF6: _mx_rows(FMT_MXBF6, 6),
     FMT_MXFP4R: _mx_rows(FMT_MXFP4, 4, True), FMT_MXFP8R: _mx_rows(FMT_MXFP8, 8, True),
@@ -843,9 +919,10 @@ ROW_FORMATS = {
 
 
 def _fmt_word(spec: CodecSpec, L: Layout) -> int:
-    """Header word 7: the hi-row format; with 6-bit or rotated MX rows or outlier rows (with_mx_elem, with_mx_rot,
-    with_outliers) the lo-row format too, in bits 8-15."""
-    return L.hi_fmt | L.lo_fmt << 8 if spec.mx_elem != FMT_MXFP4 or spec.mx_rot or spec.outliers else L.hi_fmt
+    """Header word 7: the hi-row format; with 6-bit or rotated MX rows, outlier rows or rotated int rows (with_mx_elem,
+    with_mx_rot, with_outliers, with_row_rot) the lo-row format too, in bits 8-15."""
+    both = spec.mx_elem != FMT_MXFP4 or spec.mx_rot or spec.outliers or spec.row_rot
+    return L.hi_fmt | L.lo_fmt << 8 if both else L.hi_fmt
 
 
 def _header(spec: CodecSpec, L: Layout) -> torch.Tensor:
@@ -904,8 +981,10 @@ def _encode_cpu(x, spec, L, lo_mask):
     if spec.scale_mode == SC_TOKEN:
         scales = torch.zeros(B, S)
         for is_lo, fmt, qmax in ((False, L.hi_fmt, spec.qmax_hi), (True, L.lo_fmt, spec.qmax_lo)):
-            if not ROW_FORMATS[fmt].self_scaled:   # an outlier row: the max-abs of what its 8 outliers leave
-                am = (_top8(xf.reshape(B * S, H))[2].reshape(B, S, H) if fmt in OUT_TWIN.values() else xf).abs().amax(-1)
+            if not ROW_FORMATS[fmt].self_scaled:   # an outlier row: the max-abs of what its 8 outliers leave;
+                rows = xf.reshape(B * S, H)        # a rotated row: that of y = H128 x / 8
+                am = (_top8(rows)[2].reshape(B, S, H) if fmt in OUT_TWIN.values() else
+                      _rot128(rows, 0.125).reshape(B, S, H) if fmt in ROW_ROT_TWIN.values() else xf).abs().amax(-1)
                 scales = torch.where(lo_mask if is_lo else ~lo_mask, am / float(qmax), scales)
     elif spec.scale_mode == SC_WINDOW:
         scales = torch.where(lo_mask[..., None], xf.abs(), torch.zeros_like(xf)).amax(dim=(1, 2))
@@ -1083,7 +1162,7 @@ def fork_supported(spec: CodecSpec, selection: str = "ratio") -> bool:
     int8_token_keep, mixed_int4_int8, mixed_int2_int8).  Everything else keeps the per-variant ``fake_quant``."""
     uses_kvar(spec, selection)       # an unknown selection: ValueError
     return (selection == "ratio" and spec.native_wire == NATIVE and spec.mx_elem == FMT_MXFP4 and not spec.mx_rot
-            and not spec.outliers
+            and not spec.outliers and not spec.row_rot
             and spec.scale_mode in (SC_TOKEN, SC_WINDOW)
             and (spec.hi_fmt, spec.qmax_hi) in _FORK_ROWS and (spec.lo_fmt, spec.qmax_lo) in _FORK_ROWS)
 

@@ -56,6 +56,8 @@ class Params:
                                              # every block (codec/wire.py with_mx_rot); "none": the blocks themselves
     outliers: str = "none"                   # "top8": a per-token int codec sends the 8 largest channels of every int
                                              # row exactly beside the row (codec/wire.py with_outliers); "none": not
+    row_rot: str = "none"                    # "h128": a per-token int codec quantizes the 128-point Hadamard transform
+                                             # of every 128-channel block of its int rows (codec/wire.py with_row_rot)
     sweep_fork: bool = False                 # sweeps: all (method, ratio) variants of a boundary layer from one
                                              # codec.fake_quant_fork pass (bit-identical to the per-variant path)
     lrp_engine: str = "auto"                 # relevance pass: "auto" (HIP engine on a GPU, autograd on the CPU) |
@@ -127,6 +129,11 @@ class Params:
             spec = wire.CODECS.get(self.codec) or wire.CODECS["passthrough"]
             spec = wire.with_mx_elem(wire.with_native_wire(spec, self.native_wire), self.mx_elem)
             wire.with_outliers(wire.with_mx_rot(spec, self.mx_rot), self.outliers)
+        if self.row_rot != "none":
+            from .codec import wire   # the same, for rotated int rows
+            spec = wire.CODECS.get(self.codec) or wire.CODECS["passthrough"]
+            spec = wire.with_mx_elem(wire.with_native_wire(spec, self.native_wire), self.mx_elem)
+            wire.with_row_rot(wire.with_outliers(wire.with_mx_rot(spec, self.mx_rot), self.outliers), self.row_rot)
 
 
 def resolve_device(p: Params) -> str:

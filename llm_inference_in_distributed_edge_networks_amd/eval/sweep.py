@@ -70,6 +70,7 @@ class SweepConfig:
     mx_elem: str = "fp4"               # element type of the codecs' MXFP4 rows (codec.wire.with_mx_elem)
     mx_rot: str = "none"               # "h32": the codecs' MX rows in the Hadamard basis (codec.wire.with_mx_rot)
     outliers: str = "none"             # "top8": the codecs' per-token int rows + 8 exact channels (with_outliers)
+    row_rot: str = "none"              # "h128": the codecs' per-token int rows in the Hadamard basis (with_row_rot)
     fork: bool = False                 # fake-quantize the variants of a boundary layer with codec.fake_quant_fork
 
     def rows(self) -> list:
@@ -168,9 +169,9 @@ class SweepEngine:
         return base, saved, imp
 
     def _codec(self, name: str) -> C.CodecSpec:
-        """Codec ``name`` with the sweep's native wire, MX element type, MX rotation and outliers."""
+        """Codec ``name`` with the sweep's native wire, MX element type, MX rotation, outliers and row rotation."""
         spec = C.with_mx_elem(C.with_native_wire(C.get_codec(name), self.sc.native_wire), self.sc.mx_elem)
-        return C.with_outliers(C.with_mx_rot(spec, self.sc.mx_rot), self.sc.outliers)
+        return C.with_row_rot(C.with_outliers(C.with_mx_rot(spec, self.sc.mx_rot), self.sc.outliers), self.sc.row_rot)
 
     def _spec_at(self, name: str, L: int) -> C.CodecSpec:
         """Codec ``name`` at the boundary after layer L (relevance-allocated group plan for head-group codecs)."""

@@ -53,11 +53,12 @@ class BoundaryConfig:
     mx_elem: str = "fp4"          # element type of the codec's MXFP4 rows: "fp4" | "e2m3" | "e3m2" (MXFP6 rows)
     mx_rot: str = "none"          # "h32": the codec's MX rows quantize the Hadamard-rotated blocks (with_mx_rot)
     outliers: str = "none"        # "top8": the codec's per-token int rows carry their 8 largest channels exactly
+    row_rot: str = "none"         # "h128": the codec's per-token int rows quantize the Hadamard-rotated 128-channel blocks
 
     @property
     def spec(self) -> C.CodecSpec:
         spec = C.with_mx_elem(C.with_native_wire(C.get_codec(self.codec), self.native_wire), self.mx_elem)
-        return C.with_outliers(C.with_mx_rot(spec, self.mx_rot), self.outliers)
+        return C.with_row_rot(C.with_outliers(C.with_mx_rot(spec, self.mx_rot), self.outliers), self.row_rot)
 
     def spec_for(self, boundary: int | None, hidden: int) -> C.CodecSpec:
         """The codec of the boundary after layer ``boundary``: with its relevance-allocated group plan for the

@@ -8,7 +8,8 @@
 ``name@wire`` is codec ``name`` with its activation-dtype rows on the 16-bit wire ``wire`` (``with_native_wire``),
 ``name@e2m3`` / ``name@e3m2`` with its MXFP4 rows as MXFP6 rows of that element type (``with_mx_elem``), ``name@rot``
 with its MX rows Hadamard-rotated (``with_mx_rot``), ``name@top8`` with the 8 largest channels of its per-token int
-rows kept exact (``with_outliers``); modifiers chain: ``mxfp4@e2m3@rot``.
+rows kept exact (``with_outliers``), ``name@h128`` with those rows Hadamard-rotated per 128-channel block
+(``with_row_rot``); modifiers chain: ``mxfp4@e2m3@rot``.
 
 Every codec packs the same activations ([B * S, H], randn with one massive channel) into its own preallocated
 message (the pack kernel alone: selection and statistics run once, before) and decodes it into a preallocated
@@ -109,7 +110,8 @@ def main():
             spec = C.get_codec(base)
             for mod in mods:
                 spec = C.with_mx_elem(spec, mod) if mod in W.MX_ELEMS else C.with_mx_rot(spec, "h32") if mod == "rot" \
-                    else C.with_outliers(spec, mod) if mod in W.OUTLIERS else C.with_native_wire(spec, mod)
+                    else C.with_outliers(spec, mod) if mod in W.OUTLIERS else C.with_row_rot(spec, mod) \
+                    if mod in W.ROW_ROTS else C.with_native_wire(spec, mod)
             if C.wire.needs_plan(spec):
                 spec = C.wire.with_plan(spec, (a.plan_bits,) * (H // 64))
             L = C.layout(spec, B, S, H, C.wire.num_lo(spec, a.ratio, S), dtype)

@@ -141,17 +141,19 @@ def main():
         # "name@bitsr" = over the LRP relevance (round 3's first-order allocator), "name@bitsu" = the same width in
         # every group (uniform plan, the ablation).  MX codecs: "name@e2m3" / "name@e3m2" = MXFP6 rows of that element
         # type, "name@rot" = Hadamard-rotated MX rows; they chain ("mxfp4@e2m3@rot").  Per-token int codecs: "name@top8" =
-        # outlier rows
+        # outlier rows, "name@h128" = Hadamard-rotated int rows
         base, *mods = codec.split("@")
         elem = next((x for x in mods if x in C.wire.MX_ELEMS), "fp4")
         top = next((x for x in mods if x in C.wire.OUTLIERS), "none")
-        bits = next((x for x in mods if x != "rot" and x not in C.wire.MX_ELEMS and x not in C.wire.OUTLIERS), "")
+        rrot = next((x for x in mods if x in C.wire.ROW_ROTS), "none")
+        bits = next((x for x in mods if x != "rot" and x not in C.wire.MX_ELEMS and x not in C.wire.OUTLIERS
+                     and x not in C.wire.ROW_ROTS), "")
         kind = bits[-1] if bits[-1:] in ("u", "r") else "s"
         avg = float(bits.rstrip("ur") or 4.0)
         table = {"u": None, "r": grel, "s": {"relevance": grel, "sensitivity": gsens}}[kind]
         sc = SweepConfig(METHODS, layers, ratios, codec=base, head_weights=hw, group_relevance=table,
                          group_avg_bits=avg, mx_elem=elem, mx_rot="h32" if "rot" in mods else "none",
-                         outliers=top)
+                         outliers=top, row_rot=rrot)
         eng_s = SweepEngine(m, sc, keep_windows=True)
         res = run_sweep(eng_s, batches(ev, wins, a.batch, bos=a.bos if a.bos >= 0 else None))
         nll, wts = eng_s.window_results()            # [N, methods, layers, ratios], [N]
