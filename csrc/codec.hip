@@ -17,12 +17,14 @@
 // Activations are bf16 or fp32 (the fp32 execution mode); row format 4 keeps a row in fp32 (the reference leaves
 // its un-selected tokens in fp32, Experiments/Qwen2-0.5B/qwen_layer_wise.py:54-70).
 #include "common.h"
+#include <utility>
 
 enum { FMT_BF16 = 0, FMT_INT8 = 1, FMT_INT4 = 2, FMT_INT2 = 3, FMT_F32 = 4, FMT_MXFP4 = 5, FMT_MXFP8 = 6, FMT_GRP = 7,
        FMT_GRPR = 8, FMT_F16 = 9, FMT_F16S = 10, FMT_MXFP6 = 11, FMT_MXBF6 = 12,
        FMT_MXFP4R = 13, FMT_MXFP8R = 14, FMT_MXFP6R = 15, FMT_MXBF6R = 16,
        FMT_INT8O = 17, FMT_INT4O = 18, FMT_INT2O = 19,
-       FMT_INT8R = 20, FMT_INT4R = 21, FMT_INT2R = 22 };
+       FMT_INT8R = 20, FMT_INT4R = 21, FMT_INT2R = 22,
+       FMT_INT8F = 23, FMT_INT4F = 24, FMT_INT2F = 25 };
 // Outlier rows (FMT_INT8O / FMT_INT4O / FMT_INT2O; codec/wire.py with_outliers resolves the int classes of a per-token
 // codec to them): [the plain twin's code bytes][8 fp32 values][8 uint16 channels], the twin's bytes + OUT_TAIL.  The 8
 // channels with the largest abs_bits(x) (NaN > Inf > finite; ties to the lower channel), listed in that order, cross
@@ -66,6 +68,30 @@ __device__ __forceinline__ int rr_twin(int fmt) {   // a rotated int row's plain
     if (is_rr_fmt(fmt)) return fmt - (FMT_INT8R - FMT_INT8);
   }
   return fmt;
+}
+// Row-rotated per-token int rows (FMT_INT8F / FMT_INT4F / FMT_INT2F; with_row_rot "full"): the plain twin's bytes again,
+// but codes and scale describe y = e H x of the whole row - one massive channel is spread over all H channels, so the
+// row's max|y| falls by up to sqrt(H), not sqrt(128).  H = 2^n (n = 7 .. 12): the natural-order Sylvester matrix, stages
+// at strides 1 .. 2^(n-1), e = 2^-floor(n/2), decode factor s 2^-ceil(n/2) - at H = 128 the h128 row.  H = 28 2^m (m = 5,
+// 6, 7: 896, 1792, 3584; channel a 2^m + b): H = H28 (x) H_2^m with H28 the Paley type II matrix of make_h28.  Encode: the
+// m Sylvester stages along b, the 28-point stage out[a'] = sum_a H28[a'][a] t[a] in ascending a from +-t[0] (h28_dot:
+// the order is part of the format - it is what makes non-integer rows byte-identical to the CPU's), one multiply by
+// e = 2^-(2 + floor(m/2)).  Decode: the codes as floats, the 28-point stage (H28 is symmetric; |sum| <= 3584 * 127:
+// exact), the m stages, one multiply by s d with d = fp32(1/28) 2^(2 + floor(m/2) - m), s d rounded once.  No add follows
+// a multiply.  The unit is the token row; a finite row overflows from a max-abs of about 2^(127 - log2 H).  Where it
+// runs: rot_full_row, in the RF instantiations of pack_kernel / unpack_kernel under the RR instantiations' rules
+// (SC_TOKEN only; not next to head-group, 16-bit, 6-bit, rotated MX, outlier or h128 rows; header word 7 names both
+// formats).
+__device__ __forceinline__ bool is_rf_fmt(int fmt) { return fmt >= FMT_INT8F && fmt <= FMT_INT2F; }
+template <bool RF>
+__device__ __forceinline__ int rf_twin(int fmt) {   // a row-rotated int row's plain twin, any other format itself
+  if constexpr (RF) {
+    if (is_rf_fmt(fmt)) return fmt - (FMT_INT8F - FMT_INT8);
+  }
+  return fmt;
+}
+constexpr bool rf_size_ok(int H) {   // 2^7 .. 2^12, or 28 * 2^m for m = 5, 6, 7
+  return (H >= 128 && H <= 4096 && !(H & (H - 1))) || H == 896 || H == 1792 || H == 3584;
 }
 // 16-bit wire formats of the rows a codec keeps in the activation dtype (codec/wire.py with_native_wire: the NATIVE
 // class of a codec resolves to one of them instead of the activation dtype, so fp32 activations cross at 2 B per
@@ -159,8 +185,11 @@ struct CodecArgs {
   int grp_code_bytes;           // FMT_GRP / FMT_GRPR: sum over groups of 8 b_g (row = codes + 4 G scale bytes)
 };
 
-template <bool W16, bool MX6, bool MXR = false, bool OUT = false, bool RR = false>
+template <bool W16, bool MX6, bool MXR = false, bool OUT = false, bool RR = false, bool RF = false>
 __device__ __forceinline__ int fmt_row_bytes(int fmt, int H) {
+  if constexpr (RF) {    // a row-rotated int row has the bytes of its plain twin
+    if (is_rf_fmt(fmt)) return fmt == FMT_INT8F ? H : fmt == FMT_INT4F ? H / 2 : H / 4;
+  }
   if constexpr (RR) {    // a rotated int row has the bytes of its plain twin
     if (is_rr_fmt(fmt)) return fmt == FMT_INT8R ? H : fmt == FMT_INT4R ? H / 2 : H / 4;
   }
@@ -184,12 +213,12 @@ __device__ __forceinline__ int fmt_row_bytes(int fmt, int H) {
   return fmt == FMT_F32 ? 4 * H : fmt == FMT_BF16 ? 2 * H : fmt == FMT_INT8 ? H : fmt == FMT_INT4 ? H / 2 :
          fmt == FMT_MXFP4 ? H / 2 + H / 32 : fmt == FMT_MXFP8 ? H + H / 32 : H / 4;
 }
-template <bool ROT, bool W16, bool MX6, bool MXR = false, bool OUT = false, bool RR = false>
+template <bool ROT, bool W16, bool MX6, bool MXR = false, bool OUT = false, bool RR = false, bool RF = false>
 __device__ __forceinline__ int row_bytes(const CodecArgs& a, int fmt) {
   if constexpr (ROT) {
     if (fmt == FMT_GRPR) return a.grp_code_bytes + 4 * (a.H / 64);
   }
-  return fmt == FMT_GRP ? a.grp_code_bytes + 4 * (a.H / 64) : fmt_row_bytes<W16, MX6, MXR, OUT, RR>(fmt, a.H);
+  return fmt == FMT_GRP ? a.grp_code_bytes + 4 * (a.H / 64) : fmt_row_bytes<W16, MX6, MXR, OUT, RR, RF>(fmt, a.H);
 }
 // Formats whose rows carry their own scales (or none): no entry in the message's scale section.  A macro, and the
 // rotated format joined with `|`: the compiler simplifies the body of an inlined function on its own first, and the
@@ -359,20 +388,20 @@ __device__ __forceinline__ void kvar_prefix(const CodecArgs& a, int b, int& Kb, 
 // among the class's rows of its window (lo_prefix), the class's rows of the windows before (b k / b (S - k) for fixed
 // k, the k vector's prefix sum for variable k, whose hi section starts right after the Sum k lo rows).
 struct RowSlot { uint8_t* p; int fmt, qmax, b; };
-template <bool ROT, bool W16, bool MX6, bool MXR = false, bool OUT = false, bool RR = false>
+template <bool ROT, bool W16, bool MX6, bool MXR = false, bool OUT = false, bool RR = false, bool RF = false>
 __device__ __forceinline__ RowSlot row_slot(const CodecArgs& a, int row) {
   const int b = row / a.S, j = row - b * a.S;
   const uint32_t* mask = (const uint32_t*)(a.msg + a.off_mask) + (size_t)b * a.mw;
   bool is_lo;
   const int slot_lo = lo_prefix(mask, a.mw, j, is_lo);
   const int fmt = is_lo ? a.lo_fmt : a.hi_fmt;
-  const int rb = row_bytes<ROT, W16, MX6, MXR, OUT, RR>(a, fmt);
+  const int rb = row_bytes<ROT, W16, MX6, MXR, OUT, RR, RF>(a, fmt);
   uint8_t* p;
   if (a.off_kvec >= 0) {
     int Kb, Kt;
     kvar_prefix(a, b, Kb, Kt);
-    const long long off_hi = a.off_lo + (((long long)Kt * row_bytes<ROT, W16, MX6, MXR, OUT, RR>(a, a.lo_fmt) + 15) &
-                                       ~15ll);
+    const long long off_hi =
+        a.off_lo + (((long long)Kt * row_bytes<ROT, W16, MX6, MXR, OUT, RR, RF>(a, a.lo_fmt) + 15) & ~15ll);
     p = is_lo ? a.msg + a.off_lo + ((size_t)Kb + slot_lo) * rb
               : a.msg + off_hi + ((size_t)b * a.S - Kb + (j - slot_lo)) * rb;
   } else {
@@ -1079,17 +1108,232 @@ __device__ __forceinline__ void out_patch(float (&o)[8], const OutPairs& p, int 
   if (p.bad) fill8(o, __builtin_nanf(""));
 }
 
+// ---- Row-rotated per-token int rows: one Hadamard transform of the whole row ------------------------------------------
+// The wave holds the row as everywhere else: v[NCH][8], channel = (64 c + lane) 8 + e.
+// H = 2^n, registers and cross-lane moves only: strides 1 .. 64 are wht_row16 per chunk; stride 128 pairs lane ^ 16 and
+// stride 256 lane ^ 32 (wht_xrow: v_permlane16_swap / v_permlane32_swap of a value with itself hand every lane the pair
+// (even side, odd side) - the lane with the stride bit set holds the odd side, negates it, and both add); strides 512,
+// 1024, 2048 are butterflies between the chunk registers v[c] and v[c ^ 1], v[c ^ 2], v[c ^ 4].  A stage whose stride
+// is not below H is skipped on a wave-uniform condition.  Every lane is at the moves: chunks and lanes past H hold
+// zeros and rotate zeros among themselves (a pair of lanes or chunks is past H together or not at all).
+template <bool X32>
+__device__ __forceinline__ void wht_xrow(float (&v)[8]) {   // the butterfly between lanes l and l ^ 16 (X32: l ^ 32)
+  const uint32_t lane = threadIdx.x & 63;
+  const uint32_t sg = X32 ? (lane & 32u) << 26 : (lane & 16u) << 27;
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    const uint32_t u = __float_as_uint(v[e]);
+    const auto r = X32 ? __builtin_amdgcn_permlane32_swap(u, u, false, false)
+                       : __builtin_amdgcn_permlane16_swap(u, u, false, false);
+    v[e] = __uint_as_float(r[0]) + __uint_as_float(r[1] ^ sg);   // r[0]: the side with the bit clear, r[1]: with it set
+  }
+}
+__device__ __forceinline__ void wht_lane4(float (&v)[8]) {   // the butterfly between lanes l and l ^ 4 (wht_row16's)
+  const uint32_t s4 = (threadIdx.x & 4u) << 29;
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    const uint32_t u = __float_as_uint(v[e]);
+    v[e] = __uint_as_float(quad_mov<DPP_QUAD_REV>(quad_mov<DPP_ROW_HALF_MIRROR>(u))) + __uint_as_float(u ^ s4);
+  }
+}
+template <int NCH>
+__device__ __forceinline__ void wht_pow2_row(float (&v)[NCH][8], int H) {
+#pragma unroll
+  for (int c = 0; c < NCH; ++c) wht_row16(v[c]);
+  if (H > 128) {
+#pragma unroll
+    for (int c = 0; c < NCH; ++c) wht_xrow<false>(v[c]);
+  }
+  if (H > 256) {
+#pragma unroll
+    for (int c = 0; c < NCH; ++c) wht_xrow<true>(v[c]);
+  }
+#pragma unroll
+  for (int h = 1; h < NCH; h <<= 1) {
+    if (H <= 512 * h) continue;
+#pragma unroll
+    for (int c = 0; c < NCH; ++c) {
+      if (c & h) continue;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        const float x = v[c][e], y = v[c + h][e];
+        v[c][e] = x + y;
+        v[c + h][e] = x - y;
+      }
+    }
+  }
+}
+
+// H = 28 2^m.  The signs of H28, at compile time from the Paley construction for q = 13: chi the quadratic character mod
+// 13, Q[i][j] = chi(i - j), C = [[0, 1'], [1, Q]] (14 x 14, symmetric as 13 = 1 mod 4, zero diagonal),
+// H28 = C (x) [[1, 1], [1, -1]] + I14 (x) [[1, -1], [-1, -1]]: entries +-1, symmetric, H28 H28 = 28 I.
+struct H28Signs { signed char s[28][28]; };
+constexpr int chi13(int x) {
+  x = (x % 13 + 13) % 13;
+  if (x == 0) return 0;
+  for (int k = 1; k < 13; ++k)
+    if (k * k % 13 == x) return 1;
+  return -1;
+}
+constexpr H28Signs make_h28() {
+  H28Signs t{};
+  for (int i = 0; i < 14; ++i)
+    for (int j = 0; j < 14; ++j) {
+      const int c = i == 0 && j == 0 ? 0 : i == 0 || j == 0 ? 1 : chi13(i - j);
+      for (int r = 0; r < 2; ++r)
+        for (int q = 0; q < 2; ++q)
+          t.s[2 * i + r][2 * j + q] = (signed char)(c * (r && q ? -1 : 1) + (i == j ? (r || q ? -1 : 1) : 0));
+    }
+  return t;
+}
+// out = sum_a H28[I][a] t[a], in ascending a from +-t[0].  I and the a's are template constants, so every sign is a
+// constant expression and the stage is 27 plain adds / subtracts per output: no table in memory, no register indexed
+// by data.
+template <int I, int... A>
+__device__ __forceinline__ float h28_dot(const float (&t)[28], std::integer_sequence<int, A...>) {
+  constexpr H28Signs S = make_h28();
+  float acc = S.s[I][0] > 0 ? t[0] : -t[0];
+  ((acc = S.s[I][A + 1] > 0 ? acc + t[A + 1] : acc - t[A + 1]), ...);
+  return acc;
+}
+// o[i] = row BASE + (i ^ XR) of H28 t, i = 0 .. N - 1
+template <int BASE, int XR, int... I>
+__device__ __forceinline__ void h28_rows(const float (&t)[28], float (&o)[sizeof...(I)], std::integer_sequence<int, I...>) {
+  ((o[I] = h28_dot<BASE + (I ^ XR)>(t, std::make_integer_sequence<int, 27>{})), ...);
+}
+
+// The 28-point stage runs along a, at stride 2^m channels, so the row goes through a per-wave LDS slice of H floats in
+// natural channel order (float index = channel): written as the lanes hold it (two b128 per chunk), read back by
+// column - b32 reads of t[a] = slice[a 2^m + b] for a = 0 .. 27 -, the outputs written back the same way and the
+// lane-linear image read again (two b128 per chunk).  The 2^m columns over the 64 lanes:
+//   m = 5 (NCH 2): two lanes per column, b = lane & 31; both read all 28 inputs, lane half h = lane >> 5 computes the 14
+//          outputs a' = 14 h .. 14 h + 13 (the two halves run different signs, so they take the two sides of one branch);
+//   m = 6 (NCH 4): one lane per column, b = lane;
+//   m = 7 (NCH 8): two columns per lane, b = lane and lane + 64, one after the other.
+// Bank model (64 banks of 4 bytes; a b32 access is conflict-free when its 64 lanes hit 64 banks or share an address, a
+// b128 access is served 16 lanes at a time, a lane covering the 4 banks of its 16-byte slot, slot mod 16):
+//   column reads: bank = (a 2^m + b) mod 64.  m = 6, 7: b mod 64 = lane - 64 banks.  m = 5: lanes l and l + 32 read one
+//     address (a broadcast), the 32 columns hit banks 32 (a & 1) + b - conflict-free.
+//   column writes: m = 6, 7 as the reads.  m = 5: with o[i] = output 14 h + i the halves would write addresses 448
+//     floats = 14 * 128 B = 0 mod 256 B apart - the same bank, 2-way.  So half 1 holds its outputs pairwise swapped,
+//     o[i] = output 14 + (i ^ 1): write i goes to banks 32 (i & 1) + b for half 0 and 32 (~i & 1) + b for half 1 -
+//     conflict-free.
+//   chunk accesses: lane l's slots are 2 (64 c + l) and + 1; taken in that order, lanes l and l + 8 of a 16-lane group
+//     collide (slot mod 16 = 2 l mod 16), 2-way.  So lanes with bit 3 set take their two slots in the other order: access
+//     k touches slot 2 l + (k ^ ((l >> 3) & 1)), lanes 0 - 7 of a group cover the 8 slots of one parity and lanes 8 - 15
+//     those of the other - conflict-free.
+// Only the wave touches its slice: no workgroup barrier; the wavefront-scope fences of mx6_wave_sync order one lane's
+// accesses against the others'.  A lane's own column (m = 6, 7) is read and written by that lane alone, in program
+// order.  Lanes whose channels lie past H take no part in the chunk accesses and keep their zeros.
+constexpr int RF_M(int nch) { return nch == 2 ? 5 : nch == 4 ? 6 : 7; }
+template <int NCH>
+__device__ __forceinline__ void h28_stage_lds(float (&v)[NCH][8], int H, float* __restrict__ slice) {
+  constexpr int M = RF_M(NCH), W = 1 << M;
+  const int lane = threadIdx.x & 63;
+  const bool flip = (lane >> 3) & 1;
+#pragma unroll
+  for (int c = 0; c < NCH; ++c) {
+    const int col = (c * 64 + lane) * 8;
+    if (col >= H) continue;
+    const f32x4_t lo = {v[c][0], v[c][1], v[c][2], v[c][3]}, hi = {v[c][4], v[c][5], v[c][6], v[c][7]};
+    *(f32x4_t*)(slice + col + (flip ? 4 : 0)) = flip ? hi : lo;
+    *(f32x4_t*)(slice + col + (flip ? 0 : 4)) = flip ? lo : hi;
+  }
+  mx6_wave_sync();
+  if constexpr (M == 5) {
+    const int b = lane & 31, half = lane >> 5;
+    float t[28], o[14];
+#pragma unroll
+    for (int a = 0; a < 28; ++a) t[a] = slice[a * W + b];
+    if (half) h28_rows<14, 1>(t, o, std::make_integer_sequence<int, 14>{});
+    else h28_rows<0, 0>(t, o, std::make_integer_sequence<int, 14>{});
+    mx6_wave_sync();   // the column's other lane has read it
+    // o[i] is output 14 half + (i ^ half): even i at row 14 half + i + half, odd i at 14 half + i - half
+    float* pe = slice + (14 * half + half) * W + b;
+    float* po = slice + (14 * half - half) * W + b;
+#pragma unroll
+    for (int i = 0; i < 14; ++i) (i & 1 ? po : pe)[i * W] = o[i];
+  } else {
+#pragma unroll
+    for (int j = 0; j < W / 64; ++j) {
+      float* p = slice + 64 * j + lane;
+      float t[28], o[28];
+#pragma unroll
+      for (int a = 0; a < 28; ++a) t[a] = p[a * W];
+      h28_rows<0, 0>(t, o, std::make_integer_sequence<int, 28>{});
+#pragma unroll
+      for (int a = 0; a < 28; ++a) p[a * W] = o[a];
+    }
+  }
+  mx6_wave_sync();
+#pragma unroll
+  for (int c = 0; c < NCH; ++c) {
+    const int col = (c * 64 + lane) * 8;
+    if (col >= H) continue;
+    const f32x4_t x0 = *(const f32x4_t*)(slice + col + (flip ? 4 : 0));
+    const f32x4_t x1 = *(const f32x4_t*)(slice + col + (flip ? 0 : 4));
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      v[c][e] = flip ? x1[e] : x0[e];
+      v[c][4 + e] = flip ? x0[e] : x1[e];
+    }
+  }
+}
+// The 2^m-point part along b, in the lanes that hold a block: 32 channels = a quad, 64 = 8 lanes, 128 = a DPP row.
+template <int M>
+__device__ __forceinline__ void wht_2m(float (&v)[8]) {
+  if constexpr (M == 7) {
+    wht_row16(v);
+  } else {
+    wht8(v);
+    wht_quad(v);
+    if constexpr (M == 6) wht_lane4(v);
+  }
+}
+// floats of a wave's slice: a 28 2^m row exists at NCH 2, 4, 8 only (H = 896, 1792, 3584)
+constexpr int RF_SLICE(int nch) { return nch > 1 ? 28 << RF_M(nch) : 4; }
+// v <- H v, unnormalised.  DEC: the decoder's order (the 28-point stage first; on integer codes every order is exact).
+template <int NCH, bool DEC>
+__device__ __forceinline__ void rot_full_row(float (&v)[NCH][8], int H, float* __restrict__ slice) {
+  if constexpr (NCH > 1) {
+    if (H & (H - 1)) {   // wave-uniform: 28 2^m
+      if constexpr (!DEC) {
+#pragma unroll
+        for (int c = 0; c < NCH; ++c) wht_2m<RF_M(NCH)>(v[c]);
+      }
+      h28_stage_lds<NCH>(v, H, slice);
+      if constexpr (DEC) {
+#pragma unroll
+        for (int c = 0; c < NCH; ++c) wht_2m<RF_M(NCH)>(v[c]);
+      }
+      return;
+    }
+  }
+  wht_pow2_row<NCH>(v, H);
+}
+// e and d of the comment at is_rf_fmt: ctz(H) = n, or m + 2
+__device__ __forceinline__ float pow2f(int k) { return __uint_as_float((uint32_t)(127 + k) << 23); }
+__device__ __forceinline__ float rf_enc_scale(int H) {
+  const int n = __builtin_ctz(H);
+  return H & (H - 1) ? pow2f(-(2 + (n - 2) / 2)) : pow2f(-(n / 2));
+}
+__device__ __forceinline__ float rf_dec_scale(int H) {
+  const int n = __builtin_ctz(H);
+  return H & (H - 1) ? (1.0f / 28.0f) * pow2f(2 - (n - 1) / 2) : pow2f(-((n + 1) / 2));
+}
+
 template <int NCH, class T, bool ROT = false, bool W16 = false, bool MX6 = false, bool MXR = false, bool OUT = false,
-          bool RR = false>
+          bool RR = false, bool RF = false>
 __global__ __launch_bounds__(256) void pack_kernel(CodecArgs a) {
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= a.B * a.S) return;
   const int lane = threadIdx.x & 63;
-  const RowSlot rs = row_slot<ROT, W16, MX6, MXR, OUT, RR>(a, row);
+  const RowSlot rs = row_slot<ROT, W16, MX6, MXR, OUT, RR, RF>(a, row);
   uint8_t* dst = rs.p;
   const bool orow = OUT && is_out_fmt(rs.fmt);   // an outlier row: fmt is its plain twin's
   const bool rrow = RR && is_rr_fmt(rs.fmt);     // a rotated int row: fmt is its plain twin's
-  const int fmt = rr_twin<RR>(out_twin<OUT>(rs.fmt)), qmax = rs.qmax, b = rs.b;
+  const bool frow = RF && is_rf_fmt(rs.fmt);     // a row-rotated int row: the same
+  const int fmt = rf_twin<RF>(rr_twin<RR>(out_twin<OUT>(rs.fmt))), qmax = rs.qmax, b = rs.b;
   float v[NCH][8];
   load_row8<NCH>((const T*)a.x + (size_t)row * a.H, a.H, v);
   float* scales = (float*)(a.msg + a.off_scale);
@@ -1101,6 +1345,17 @@ __global__ __launch_bounds__(256) void pack_kernel(CodecArgs a) {
 #pragma unroll
         for (int e = 0; e < 8; ++e) v[c][e] *= 0.125f;
       }
+    }
+  }
+  if constexpr (RF) {   // a row-rotated int row: v becomes y = e H x of the whole row; from here on it is its plain twin's
+    __shared__ __attribute__((aligned(16))) float rf_lds[4][RF_SLICE(NCH)];
+    if (frow) {         // wave-uniform: the row's format
+      rot_full_row<NCH, false>(v, a.H, rf_lds[threadIdx.x >> 6]);
+      const float es = rf_enc_scale(a.H);
+#pragma unroll
+      for (int c = 0; c < NCH; ++c)
+#pragma unroll
+        for (int e = 0; e < 8; ++e) v[c][e] *= es;
     }
   }
 
@@ -1251,6 +1506,55 @@ __device__ __forceinline__ void store8(float* dst, const float (&o)[8]) {
   *(f32x4_t*)(dst + 4) = f32x4_t{o[4], o[5], o[6], o[7]};
 }
 
+// The 8 integer codes at channels col .. col + 7 of an FMT_INT8 / FMT_INT4 / FMT_INT2 row, as unpack_kernel's own loop
+// reads them (which keeps its inline copy: through this function its instantiations compile to other code)
+__device__ __forceinline__ void int_codes8(const uint8_t* __restrict__ src, int col, int fmt, int (&q)[8]) {
+  if (fmt == FMT_INT8) {
+    const u32x2_t w = *(const u32x2_t*)(src + col);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      q[e] = (int)(int8_t)((w[0] >> (8 * e)) & 255);
+      q[4 + e] = (int)(int8_t)((w[1] >> (8 * e)) & 255);
+    }
+  } else if (fmt == FMT_INT4) {
+    const uint32_t w = *(const uint32_t*)(src + col / 2);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) q[e] = ((int)(w << (28 - 4 * e))) >> 28;
+  } else {
+    const uint32_t w = *(const uint16_t*)(src + col / 4);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) q[e] = ((int)(w << (30 - 2 * e))) >> 30;
+  }
+}
+
+// A row-rotated int row: x' = (s d) H q.  The whole row - the codes of all its chunks as floats, zeros past H - is in
+// registers before the stages run, so there is no store per chunk as for the other formats; the data flow mirrors
+// pack's (rot_full_row, the decoder's order), one multiply, then the row's store8s.  fmt: the plain twin's.
+template <int NCH, class T>
+__device__ __forceinline__ void rf_unpack_row(const uint8_t* __restrict__ src, int H, int fmt, float s,
+                                              T* __restrict__ out, float* __restrict__ slice) {
+  const int lane = threadIdx.x & 63;
+  float o[NCH][8];
+#pragma unroll
+  for (int c = 0; c < NCH; ++c) {
+    const int col = (c * 64 + lane) * 8;
+    int q[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (col < H) int_codes8(src, col, fmt, q);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) o[c][e] = (float)q[e];
+  }
+  rot_full_row<NCH, true>(o, H, slice);
+  const float sc = s * rf_dec_scale(H);
+#pragma unroll
+  for (int c = 0; c < NCH; ++c) {
+    const int col = (c * 64 + lane) * 8;
+    if (col >= H) continue;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) o[c][e] *= sc;
+    store8(out + col, o[c]);
+  }
+}
+
 template <int NCH, class T, bool R6 = false>
 __device__ __forceinline__ void mx6_unpack_row(const uint8_t* __restrict__ row, int H, int fmt, T* __restrict__ out,
                                                float* __restrict__ slice) {
@@ -1296,16 +1600,17 @@ __device__ __forceinline__ void mx6_unpack_row(const uint8_t* __restrict__ row, 
 }
 
 template <int NCH, class T, bool ROT = false, bool W16 = false, bool MX6 = false, bool MXR = false, bool OUT = false,
-          bool RR = false>
+          bool RR = false, bool RF = false>
 __global__ __launch_bounds__(256) void unpack_kernel(CodecArgs a) {
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= a.B * a.S) return;
   const int lane = threadIdx.x & 63;
-  const RowSlot rs = row_slot<ROT, W16, MX6, MXR, OUT, RR>(a, row);
+  const RowSlot rs = row_slot<ROT, W16, MX6, MXR, OUT, RR, RF>(a, row);
   const uint8_t* src = rs.p;
   const bool orow = OUT && is_out_fmt(rs.fmt);   // an outlier row: fmt is its plain twin's
   const bool rrow = RR && is_rr_fmt(rs.fmt);     // a rotated int row: fmt is its plain twin's
-  const int fmt = rr_twin<RR>(out_twin<OUT>(rs.fmt)), qmax = rs.qmax, b = rs.b;
+  const bool frow = RF && is_rf_fmt(rs.fmt);     // a row-rotated int row: the same
+  const int fmt = rf_twin<RF>(rr_twin<RR>(out_twin<OUT>(rs.fmt))), qmax = rs.qmax, b = rs.b;
   const float* scales = (const float*)(a.msg + a.off_scale);
   float s = 0.f;
   if (!SELF_SCALED(ROT, W16, MX6, MXR, fmt)) {
@@ -1313,7 +1618,7 @@ __global__ __launch_bounds__(256) void unpack_kernel(CodecArgs a) {
     else if (a.scale_mode == SC_WINDOW) s = scales[b];
   }
   T* out = (T*)a.x + (size_t)row * a.H;
-  if constexpr (MX6 || MXR || OUT || RR) {
+  if constexpr (MX6 || MXR || OUT || RR || RF) {
     // header word 7 of a message with 6-bit, rotated or outlier rows names both classes' formats; one that disagrees with the
     // formats this launch was given (encoded with another element type, or without the modifier) decodes to NaN - loud
     if (((const int*)a.msg)[7] != (a.hi_fmt | a.lo_fmt << 8)) {
@@ -1339,6 +1644,13 @@ __global__ __launch_bounds__(256) void unpack_kernel(CodecArgs a) {
                                      mx6_lds[threadIdx.x >> 6]);
         return;
       }
+    }
+  }
+  if constexpr (RF) {
+    __shared__ __attribute__((aligned(16))) float rf_lds[4][RF_SLICE(NCH)];
+    if (frow) {   // wave-uniform: the row's format
+      rf_unpack_row<NCH>(src, a.H, fmt, s, out, rf_lds[threadIdx.x >> 6]);
+      return;
     }
   }
   float p16 = 1.f;   // FMT_F16S: the row's p (FMT_F16: 1, an exact multiply)
@@ -1778,10 +2090,11 @@ EDGE_API int edge_rowmax(const float* in, float* out, int R, int H, hipStream_t 
 static bool has_fmt(int hi_fmt, int lo_fmt, int fmt) { return hi_fmt == fmt || lo_fmt == fmt; }
 
 template <bool PACK, int NCH, class T, bool ROT, bool W16 = false, bool MX6 = false, bool MXR = false, bool OUT = false,
-          bool RR = false>
+          bool RR = false, bool RF = false>
 static void launch_codec(dim3 grid, hipStream_t st, const CodecArgs& a) {
-  if constexpr (PACK) hipLaunchKernelGGL((pack_kernel<NCH, T, ROT, W16, MX6, MXR, OUT, RR>), grid, dim3(256), 0, st, a);
-  else hipLaunchKernelGGL((unpack_kernel<NCH, T, ROT, W16, MX6, MXR, OUT, RR>), grid, dim3(256), 0, st, a);
+  if constexpr (PACK)
+    hipLaunchKernelGGL((pack_kernel<NCH, T, ROT, W16, MX6, MXR, OUT, RR, RF>), grid, dim3(256), 0, st, a);
+  else hipLaunchKernelGGL((unpack_kernel<NCH, T, ROT, W16, MX6, MXR, OUT, RR, RF>), grid, dim3(256), 0, st, a);
 }
 
 // edge_pack / edge_unpack: argument checks, CodecArgs and the (ROT | W16 | plain) x activation dtype x NCH dispatch.
@@ -1792,7 +2105,9 @@ static void launch_codec(dim3 grid, hipStream_t st, const CodecArgs& a) {
 // A message with outlier rows goes to the OUT instantiations; with any scale mode but SC_TOKEN, or next to head-group,
 // 16-bit, 6-bit or rotated rows, it is rejected before anything is launched.  A message with rotated int rows goes to the
 // RR instantiations; with H % 128 != 0, any scale mode but SC_TOKEN, or next to head-group, 16-bit, 6-bit, rotated MX or
-// outlier rows, it is rejected the same way.
+// outlier rows, it is rejected the same way.  A message with row-rotated int rows goes to the RF instantiations; with a
+// hidden size that is neither 2^7 .. 2^12 nor 28 * 2^5 .. 28 * 2^7, any scale mode but SC_TOKEN, or next to head-group,
+// 16-bit, 6-bit, rotated MX, outlier or block-rotated (h128) rows, it is rejected the same way.
 template <bool PACK>
 static int run_codec(void* x, void* msg, long long om, long long os, long long oh, long long ol, long long okv,
                      long long opl, int B, int S, int H, int k, int hi_fmt, int lo_fmt, int scale_mode, int qmax_hi,
@@ -1811,6 +2126,11 @@ static int run_codec(void* x, void* msg, long long om, long long os, long long o
   if (out && (rot || w16 || mx6 || mxr || has_fmt(hi_fmt, lo_fmt, FMT_GRP) || scale_mode != SC_TOKEN))
     return (int)hipErrorInvalidValue;
   if (rr && (out || rot || w16 || mx6 || mxr || has_fmt(hi_fmt, lo_fmt, FMT_GRP) || scale_mode != SC_TOKEN || H % 128))
+    return (int)hipErrorInvalidValue;
+  const bool rf = has_fmt(hi_fmt, lo_fmt, FMT_INT8F) || has_fmt(hi_fmt, lo_fmt, FMT_INT4F) ||
+                  has_fmt(hi_fmt, lo_fmt, FMT_INT2F);
+  if (rf && (rr || out || rot || w16 || mx6 || mxr || has_fmt(hi_fmt, lo_fmt, FMT_GRP) || scale_mode != SC_TOKEN ||
+             !rf_size_ok(H)))
     return (int)hipErrorInvalidValue;
   if ((rot || has_fmt(hi_fmt, lo_fmt, FMT_GRP)) && (H % 64 || opl < 0 || grp_code_bytes <= 0))
     return (int)hipErrorInvalidValue;
@@ -1839,6 +2159,10 @@ static int run_codec(void* x, void* msg, long long om, long long os, long long o
   else if (rr && x_f32)
     DISPATCH_NCH(H, (launch_codec<PACK, NCH, float, false, false, false, false, false, true>(grid, st, a)));
   else if (rr) DISPATCH_NCH(H, (launch_codec<PACK, NCH, bf16_t, false, false, false, false, false, true>(grid, st, a)));
+  else if (rf && x_f32)
+    DISPATCH_NCH(H, (launch_codec<PACK, NCH, float, false, false, false, false, false, false, true>(grid, st, a)));
+  else if (rf)
+    DISPATCH_NCH(H, (launch_codec<PACK, NCH, bf16_t, false, false, false, false, false, false, true>(grid, st, a)));
   else if (x_f32) DISPATCH_NCH(H, (launch_codec<PACK, NCH, float, false>(grid, st, a)));
   else DISPATCH_NCH(H, (launch_codec<PACK, NCH, bf16_t, false>(grid, st, a)));
   return (int)hipGetLastError();

@@ -34,6 +34,8 @@ mxfp4_keep             native dtype    MXFP4           E8M0 / 32ch  Q1 with MX b
                        int2 rows of the per-token codecs            fp32 beside it; the scale is the rest's
 (the int rows above)   with_row_rot "h128": the same rows as        the plain rows' bytes of y = H128 x / 8 per
                        their rotated twins (H % 128 == 0)           128-channel block (Hadamard, DPP row moves)
+(the int rows above)   with_row_rot "full": the same rows, one      the plain rows' bytes of y = e H x, H of order
+                       rotation of the row (H = 2^n, 28 x 2^m)      H: Sylvester, or Paley H28 (x) Sylvester
 rgroup                 head groups     --              per group    every 64-channel group (one head) its
                                                                     own max-abs scale and 2/4/8-bit width
 mixed_rgroup_int8      int8            head groups     token/group  config 5 (relevance-allocated widths
@@ -81,6 +83,12 @@ Hadamard transform, at the plain row's bytes (896 = 7 x 128; the hidden size mus
 channel is spread over its block, so the row's max-abs and step fall by up to 8.  It pays where the spread spike stays
 within a few steps of the other channels - int8 rows, moderate spikes at int4; at 2 bits and for very large spikes at
 4 bits it can lose, and ``with_outliers`` is the remedy there.  Not combined with the other modifiers.
+
+``with_row_rot(spec, "full")`` rotates the whole row instead, as QuaRot / SpinQuant do: one Hadamard matrix of order H,
+the Sylvester matrix for H = 2^7 .. 2^12 and H28 (x) H_2^m (H28: Paley type II, q = 13) for H = 896, 1792, 3584; any
+other hidden size is a ``ValueError`` (12 x 2^k and 20 x 2^k sizes are out of scope).  The row's max-abs falls by up to
+sqrt(H) instead of 8: int8 rows with one x100 channel reconstruct with 3.3x less error than under ``h128``.  Where
+rotation loses - int4 with a x1000 channel, int2 - it loses by more than ``h128``; ``with_outliers`` stays the remedy.
 
 ``fake_quant_fork(x, spec, B, S, variants, importances)`` is ``fake_quant`` for a whole list of (importance source, k)
 variants of one codec at once - the sweep's step between the shared prefix and the stacked suffix: one sort per

@@ -102,6 +102,25 @@ the other channels (int8; moderate spikes at int4); at 2 bits and for very large
 ``with_outliers`` is the remedy.  Not combined with ``native_wire``, ``mx_elem``, ``mx_rot`` or ``outliers``; such
 specs are not served by ``fake_quant_fork``.
 
+Row-rotated per-token int rows.  ``with_row_rot(spec, "full")`` - the same option's other value - resolves the same
+classes to ``FMT_INT8F`` = 23, ``FMT_INT4F`` = 24, ``FMT_INT2F`` = 25: the plain row's bytes again, but codes and scale
+describe ``y = e H x`` of the whole row, as QuaRot / SpinQuant rotate the whole hidden dimension - a loud channel is
+spread over all H channels and the row's max-abs falls by up to sqrt(H), not sqrt(128).  Supported hidden sizes
+(``ROW_ROT_FULL_SIZES``; ``layout`` raises a ``ValueError`` naming them for any other, 384 and 640 included; 12 x 2^k and
+20 x 2^k sizes such as 1536 are out of scope): ``H = 2^n``, n = 7 .. 12 - H the natural-order Sylvester matrix, stages at
+strides 1 .. 2^(n-1), ``e = 2^-floor(n/2)``, decode factor ``s 2^-ceil(n/2)``, so at H = 128 the message is the ``h128``
+message apart from the format words; and ``H = 28 x 2^m``, m = 5, 6, 7 (896, 1792, 3584) - channel ``a 2^m + b``,
+``H = H28 (x) H_2^m`` with H28 the Paley type II matrix for q = 13 (``_h28``: from the formula, symmetric, +-1,
+``H28 H28 = 28 I``).  Encode: the m Sylvester stages along b; the 28-point stage ``out[a'] = sum_a H28[a'][a] t[a]``
+accumulated in fp32 in ascending a from ``+-t[0]`` (the order is part of the format: it makes non-integer rows
+byte-identical on GPU and CPU); one multiply by ``e = 2^-(2 + floor(m/2))``.  Decode: the codes as floats, the same
+28-point routine (sums at most 3584 x 127: exact), the m stages, one multiply by ``s d`` with ``d = fp32(1/28)
+2^(2 + floor(m/2) - m)``, ``s d`` rounded once.  No add follows a multiply.  The unit is the token row: a NaN / Inf
+anywhere, or a finite row whose sums overflow (max-abs from about 2^(127 - log2 H)), makes the scale and the whole
+decoded row non-finite.  Header word 7, the refusals and the combinations are ``h128``'s.  It is ahead of ``h128``
+wherever ``h128`` is ahead of the plain row, and further behind where rotation loses (int4 with a x1000 channel, int2):
+that regime is ``with_outliers``'.
+
 ``encode``/``decode`` run the gfx950 kernels of ``csrc/codec.hip`` for CUDA
 tensors and a bit-identical PyTorch implementation for CPU tensors.
 
@@ -135,6 +154,10 @@ OUT_TWIN = {FMT_INT8: FMT_INT8O, FMT_INT4: FMT_INT4O, FMT_INT2: FMT_INT2O}
 OUT_K, OUT_TAIL = 8, 48     # outliers of such a row; bytes of its tail: 8 fp32 values, 8 uint16 channels
 FMT_INT8R, FMT_INT4R, FMT_INT2R = 20, 21, 22   # per-token int rows of the Hadamard-rotated 128-channel blocks (with_row_rot)
 ROW_ROT_TWIN = {FMT_INT8: FMT_INT8R, FMT_INT4: FMT_INT4R, FMT_INT2: FMT_INT2R}
+FMT_INT8F, FMT_INT4F, FMT_INT2F = 23, 24, 25   # per-token int rows of the Hadamard-rotated whole row (with_row_rot "full")
+ROW_ROT_FULL_TWIN = {FMT_INT8: FMT_INT8F, FMT_INT4: FMT_INT4F, FMT_INT2: FMT_INT2F}
+ROW_ROT_FULL = -1           # CodecSpec.row_rot of "full": the block is the row
+ROW_ROT_FULL_SIZES = tuple(1 << n for n in range(7, 13)) + tuple(28 << m for m in (5, 6, 7))   # 2^n; 28 * 2^m
 GRP_FORMATS = (FMT_GRP, FMT_GRPR)
 SC_TOKEN, SC_WINDOW, SC_CHANNEL, SC_NONE = 0, 1, 2, 3
 CH_MAXABS, CH_MEAN = 0, 1
@@ -143,7 +166,7 @@ NATIVE_WIRES = {"native": NATIVE, "bf16": FMT_BF16, "fp16": FMT_F16, "fp16s": FM
 MX_ELEMS = {"fp4": FMT_MXFP4, "e2m3": FMT_MXFP6, "e3m2": FMT_MXBF6}                         # with_mx_elem
 MX_ROTS = {"none": 0, "h32": 32}                                                            # with_mx_rot: block size
 OUTLIERS = {"none": 0, "top8": OUT_K}                                                       # with_outliers: count
-ROW_ROTS = {"none": 0, "h128": 128}                                                         # with_row_rot: block size
+ROW_ROTS = {"none": 0, "h128": 128, "full": ROW_ROT_FULL}                                   # with_row_rot: block size
 
 
 @dataclass(frozen=True)
@@ -163,7 +186,8 @@ class CodecSpec:
     mx_elem: int = FMT_MXFP4     # row format of the FMT_MXFP4 classes on the wire (with_mx_elem)
     mx_rot: int = 0              # 32: the MX classes cross as their rotated twins (with_mx_rot); 0: as they are
     outliers: int = 0            # 8: the per-token int classes cross as their outlier twins (with_outliers); 0: as they are
-    row_rot: int = 0             # 128: the per-token int classes cross as their rotated twins (with_row_rot); 0: as they are
+    row_rot: int = 0             # 128 / ROW_ROT_FULL: the per-token int classes cross as their block- / row-rotated twins
+                                 # (with_row_rot); 0: as they are
 
 
 CODECS = {c.name: c for c in [
@@ -302,8 +326,9 @@ def with_outliers(spec: CodecSpec, name: str) -> CodecSpec:
 
 
 def with_row_rot(spec: CodecSpec, name: str) -> CodecSpec:
-    """The codec with its per-token int rows quantized in the basis of the 128-point Hadamard transform of every
-    128-channel block: "none" (the spec itself) | "h128" (module docstring).  For the specs ``with_outliers`` takes:
+    """The codec with its per-token int rows quantized in a Hadamard basis: "none" (the spec itself) | "h128" (the
+    128-point transform of every 128-channel block) | "full" (one transform of the whole row, H = 2^n or 28 * 2^m;
+    module docstring).  For the specs ``with_outliers`` takes:
     SC_TOKEN codecs with an FMT_INT8 / FMT_INT4 / FMT_INT2 class and no head-group rows; not combined with a 16-bit
     native wire, a 6-bit MX element type, rotated MX rows or outlier rows."""
     from dataclasses import replace
@@ -397,7 +422,7 @@ def _resolve(fmt: int, spec: CodecSpec, native: int) -> int:
     if spec.outliers:
         return OUT_TWIN.get(fmt, fmt)
     if spec.row_rot:
-        return ROW_ROT_TWIN.get(fmt, fmt)
+        return (ROW_ROT_FULL_TWIN if spec.row_rot == ROW_ROT_FULL else ROW_ROT_TWIN).get(fmt, fmt)
     fmt = spec.mx_elem if fmt == FMT_MXFP4 else fmt
     return MX_ROT_TWIN.get(fmt, fmt) if spec.mx_rot else fmt
 
@@ -409,7 +434,10 @@ def layout(spec: CodecSpec, B: int, S: int, H: int, k: int, dtype: torch.dtype =
         raise ValueError("hidden size must be a multiple of 32 for the packed formats")
     nf = native_fmt(dtype) if spec.native_wire == NATIVE else spec.native_wire
     hi, lo = _resolve(spec.hi_fmt, spec, nf), _resolve(spec.lo_fmt, spec, nf)
-    if spec.row_rot and H % spec.row_rot:
+    if spec.row_rot == ROW_ROT_FULL:
+        if H not in ROW_ROT_FULL_SIZES:
+            raise ValueError(f"row-rotated int rows (row_rot full) need a hidden size in {ROW_ROT_FULL_SIZES}, got {H}")
+    elif spec.row_rot and H % spec.row_rot:
         raise ValueError(f"rotated int rows need a hidden size multiple of {spec.row_rot}")
     plan = None
     if hi in GRP_FORMATS or lo in GRP_FORMATS:
@@ -727,6 +755,68 @@ def _rot128(rows: torch.Tensor, scale) -> torch.Tensor:
     return (_wht128(rows.float().reshape(n, H // 128, 128)) * scale).reshape(n, H)
 
 
+@lru_cache(maxsize=1)
+def _h28() -> torch.Tensor:
+    """The Paley type II Hadamard matrix of order 28 (q = 13), fp32 [28, 28], symmetric: Q[i][j] = chi(i - j) with chi
+    the quadratic character mod 13, C = [[0, 1'], [1, Q]] (14 x 14), H28 = C (x) [[1, 1], [1, -1]] + I14 (x) [[1, -1],
+    [-1, -1]] - the formula of csrc/codec.hip make_h28."""
+    squares = {k * k % 13 for k in range(1, 13)}
+    chi = [0] + [1 if r in squares else -1 for r in range(1, 13)]
+    C = torch.ones(14, 14)
+    C[0, 0] = 0.0
+    C[1:, 1:] = torch.tensor([[float(chi[(i - j) % 13]) for j in range(13)] for i in range(13)])
+    return torch.kron(C, torch.tensor([[1.0, 1.0], [1.0, -1.0]])) + \
+        torch.kron(torch.eye(14), torch.tensor([[1.0, -1.0], [-1.0, -1.0]]))
+
+
+def _wht_last(v: torch.Tensor) -> torch.Tensor:
+    """Unnormalised Walsh-Hadamard transform (Sylvester order) of the last dimension, a power of two, in fp32: the
+    butterflies (a, b) -> (a + b, a - b) at strides 1, 2, ... in that order, the lower index keeping the sum."""
+    lead, n, h = v.shape[:-1], v.shape[-1], 1
+    while h < n:
+        p = v.reshape(*lead, n // (2 * h), 2, h)
+        a, b = p[..., 0, :], p[..., 1, :]
+        v, h = torch.stack((a + b, a - b), -2).reshape(*lead, n), 2 * h
+    return v
+
+
+def _h28_stage(t: torch.Tensor) -> torch.Tensor:
+    """out[:, a'] = sum_a H28[a'][a] t[:, a] of fp32 [n, 28, W], accumulated in ascending a from +-t[:, 0] - the order
+    is the format's (csrc/codec.hip h28_dot)."""
+    Hm = _h28()
+    acc = Hm[:, 0, None] * t[:, 0:1, :]
+    for a in range(1, 28):
+        acc = acc + Hm[:, a, None] * t[:, a:a + 1, :]     # +-1 times t is exact: an add or a subtract of t[a]
+    return acc
+
+
+def _full_scales(H: int):
+    """(e, d) of a whole-row rotation: the encoder's y = e H x and the decoder's x' = (s d) H q.  H = 2^n: 2^-floor(n/2),
+    2^-ceil(n/2).  H = 28 * 2^m: 2^-(2 + floor(m/2)), fp32(1/28) 2^(2 + floor(m/2) - m)."""
+    if H & (H - 1) == 0:
+        n = H.bit_length() - 1
+        return 2.0 ** -(n // 2), torch.tensor(2.0 ** -((n + 1) // 2))
+    m = (H // 28).bit_length() - 1
+    return 2.0 ** -(2 + m // 2), (torch.ones(()) / 28.0) * 2.0 ** (2 + m // 2 - m)
+
+
+def _rot_full(rows: torch.Tensor, decode_scale: torch.Tensor | None = None) -> torch.Tensor:
+    """The whole-row rotation of fp32 rows [n, H], H in ROW_ROT_FULL_SIZES (channel a 2^m + b, H = H28 (x) H_2^m, or
+    the Sylvester matrix of order H).  Encoder (``decode_scale`` None): the Sylvester stages, the 28-point stage, one
+    multiply by e.  Decoder: the 28-point stage, the Sylvester stages, one multiply by ``decode_scale`` (the rows'
+    fp32 s d, [n])."""
+    n, H = rows.shape
+    e, _ = _full_scales(H)
+    v = rows.float()
+    if H & (H - 1):
+        v = v.reshape(n, 28, H // 28)
+        v = _wht_last(_h28_stage(v)) if decode_scale is not None else _h28_stage(_wht_last(v))
+        v = v.reshape(n, H)
+    else:
+        v = _wht_last(v)
+    return v * (e if decode_scale is None else decode_scale[:, None])
+
+
 def hadamard64(x: torch.Tensor) -> torch.Tensor:
     """y_g = H64 x_g / 8 for every 64-channel group of fp32 rows [n, H]: orthonormal, symmetric, its own inverse.
     The scaling by 1/8 is exact, so the only roundings are those of the 6 butterfly levels' fp32 adds."""
@@ -837,13 +927,22 @@ class RowFormat:
     unpack: Callable[[torch.Tensor, int, RowCtx], torch.Tensor]     # (bytes, n, ctx) -> fp32 rows [n, H]
 
 
-def _int_rows(fmt: int, per_byte: int, rot: bool = False) -> RowFormat:
-    """``rot``: the rotated twin (SC_TOKEN only) - the same bytes of y = H128 x / 8, whose max-abs made c.scale_row
-    (_encode_cpu); the decoder rotates the integer codes back and multiplies once, by s / 16."""
+def _row_rotated(rows: torch.Tensor, rot) -> torch.Tensor:
+    """What a rotated twin quantizes: y = H128 x / 8 of every block (``rot`` True) or y = e H x of the row ("full")."""
+    return _rot_full(rows) if rot == "full" else _rot128(rows, 0.125)
+
+
+def _int_rows(fmt: int, per_byte: int, rot=False) -> RowFormat:
+    """``rot``: a rotated twin (SC_TOKEN only) - the same bytes of y = H128 x / 8 (True) or of the whole row's y = e H x
+    ("full"), whose max-abs made c.scale_row (_encode_cpu); the decoder rotates the integer codes back and multiplies
+    once, by s / 16 or s d."""
     def pack(rows, c):
-        return _pack_rows(_qcodes(_rot128(rows, 0.125) if rot else rows, c.spec, c.is_lo, c.scale_row, c.ch_scale), fmt)
+        return _pack_rows(_qcodes(_row_rotated(rows, rot) if rot else rows, c.spec, c.is_lo, c.scale_row, c.ch_scale),
+                          fmt)
 
     def unpack(raw, n, c):
+        if rot == "full":
+            return _rot_full(_unpack_rows(raw, fmt, n, c.H), c.scale_row * _full_scales(c.H)[1])
         if rot:
             return _rot128(_unpack_rows(raw, fmt, n, c.H), (c.scale_row * 0.0625)[:, None, None])
         return _dequant(_unpack_rows(raw, fmt, n, c.H), c.spec, c.is_lo, c.scale_row, c.ch_scale)
@@ -906,6 +1005,8 @@ ROW_FORMATS = {
     FMT_INT8O: _out_rows(FMT_INT8, 1), FMT_INT4O: _out_rows(FMT_INT4, 2), FMT_INT2O: _out_rows(FMT_INT2, 4),
     FMT_INT8R: _int_rows(FMT_INT8, 1, True), FMT_INT4R: _int_rows(FMT_INT4, 2, True),
     FMT_INT2R: _int_rows(FMT_INT2, 4, True),
+    FMT_INT8F: _int_rows(FMT_INT8, 1, "full"), FMT_INT4F: _int_rows(FMT_INT4, 2, "full"),
+    FMT_INT2F: _int_rows(FMT_INT2, 4, "full"),
     FMT_MXFP4: _mx_rows(FMT_MXFP4, 4), FMT_MXFP8: _mx_rows(FMT_MXFP8, 8),
     FMT_MXFP6: _mx_rows(FMT_MXFP6, 6), FMT_MXBF6: _mx_rows(FMT_MXBF6, 6),
     FMT_MXFP4R: _mx_rows(FMT_MXFP4, 4, True), FMT_MXFP8R: _mx_rows(FMT_MXFP8, 8, True),
@@ -982,9 +1083,10 @@ def _encode_cpu(x, spec, L, lo_mask):
         scales = torch.zeros(B, S)
         for is_lo, fmt, qmax in ((False, L.hi_fmt, spec.qmax_hi), (True, L.lo_fmt, spec.qmax_lo)):
             if not ROW_FORMATS[fmt].self_scaled:   # an outlier row: the max-abs of what its 8 outliers leave;
-                rows = xf.reshape(B * S, H)        # a rotated row: that of y = H128 x / 8
+                rows = xf.reshape(B * S, H)        # a rotated row: that of y = H128 x / 8, or of the row's y = e H x
                 am = (_top8(rows)[2].reshape(B, S, H) if fmt in OUT_TWIN.values() else
-                      _rot128(rows, 0.125).reshape(B, S, H) if fmt in ROW_ROT_TWIN.values() else xf).abs().amax(-1)
+                      _rot128(rows, 0.125).reshape(B, S, H) if fmt in ROW_ROT_TWIN.values() else
+                      _rot_full(rows).reshape(B, S, H) if fmt in ROW_ROT_FULL_TWIN.values() else xf).abs().amax(-1)
                 scales = torch.where(lo_mask if is_lo else ~lo_mask, am / float(qmax), scales)
     elif spec.scale_mode == SC_WINDOW:
         scales = torch.where(lo_mask[..., None], xf.abs(), torch.zeros_like(xf)).amax(dim=(1, 2))

@@ -57,7 +57,8 @@ class Params:
     outliers: str = "none"                   # "top8": a per-token int codec sends the 8 largest channels of every int
                                              # row exactly beside the row (codec/wire.py with_outliers); "none": not
     row_rot: str = "none"                    # "h128": a per-token int codec quantizes the 128-point Hadamard transform
-                                             # of every 128-channel block of its int rows (codec/wire.py with_row_rot)
+                                             # of every 128-channel block of its int rows (codec/wire.py with_row_rot);
+                                             # "full": one Hadamard transform of the whole row (H = 2^n or 28 * 2^m)
     sweep_fork: bool = False                 # sweeps: all (method, ratio) variants of a boundary layer from one
                                              # codec.fake_quant_fork pass (bit-identical to the per-variant path)
     lrp_engine: str = "auto"                 # relevance pass: "auto" (HIP engine on a GPU, autograd on the CPU) |

@@ -70,7 +70,8 @@ class SweepConfig:
     mx_elem: str = "fp4"               # element type of the codecs' MXFP4 rows (codec.wire.with_mx_elem)
     mx_rot: str = "none"               # "h32": the codecs' MX rows in the Hadamard basis (codec.wire.with_mx_rot)
     outliers: str = "none"             # "top8": the codecs' per-token int rows + 8 exact channels (with_outliers)
-    row_rot: str = "none"              # "h128": the codecs' per-token int rows in the Hadamard basis (with_row_rot)
+    row_rot: str = "none"              # "h128" / "full": the codecs' per-token int rows in the Hadamard basis of every
+                                       # 128-channel block / of the whole row (with_row_rot)
     fork: bool = False                 # fake-quantize the variants of a boundary layer with codec.fake_quant_fork
 
     def rows(self) -> list:

@@ -53,7 +53,8 @@ class BoundaryConfig:
     mx_elem: str = "fp4"          # element type of the codec's MXFP4 rows: "fp4" | "e2m3" | "e3m2" (MXFP6 rows)
     mx_rot: str = "none"          # "h32": the codec's MX rows quantize the Hadamard-rotated blocks (with_mx_rot)
     outliers: str = "none"        # "top8": the codec's per-token int rows carry their 8 largest channels exactly
-    row_rot: str = "none"         # "h128": the codec's per-token int rows quantize the Hadamard-rotated 128-channel blocks
+    row_rot: str = "none"         # "h128": the codec's per-token int rows quantize the Hadamard-rotated 128-channel blocks;
+                                  # "full": the Hadamard-rotated whole row (hidden size 2^n or 28 * 2^m)
 
     @property
     def spec(self) -> C.CodecSpec:

@@ -8,8 +8,8 @@
 ``name@wire`` is codec ``name`` with its activation-dtype rows on the 16-bit wire ``wire`` (``with_native_wire``),
 ``name@e2m3`` / ``name@e3m2`` with its MXFP4 rows as MXFP6 rows of that element type (``with_mx_elem``), ``name@rot``
 with its MX rows Hadamard-rotated (``with_mx_rot``), ``name@top8`` with the 8 largest channels of its per-token int
-rows kept exact (``with_outliers``), ``name@h128`` with those rows Hadamard-rotated per 128-channel block
-(``with_row_rot``); modifiers chain: ``mxfp4@e2m3@rot``.
+rows kept exact (``with_outliers``), ``name@h128`` / ``name@full`` with those rows Hadamard-rotated per 128-channel block /
+as whole rows (``with_row_rot``); modifiers chain: ``mxfp4@e2m3@rot``.
 
 Every codec packs the same activations ([B * S, H], randn with one massive channel) into its own preallocated
 message (the pack kernel alone: selection and statistics run once, before) and decodes it into a preallocated
