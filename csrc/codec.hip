@@ -24,7 +24,7 @@ enum { FMT_BF16 = 0, FMT_INT8 = 1, FMT_INT4 = 2, FMT_INT2 = 3, FMT_F32 = 4, FMT_
        FMT_MXFP4R = 13, FMT_MXFP8R = 14, FMT_MXFP6R = 15, FMT_MXBF6R = 16,
        FMT_INT8O = 17, FMT_INT4O = 18, FMT_INT2O = 19,
        FMT_INT8R = 20, FMT_INT4R = 21, FMT_INT2R = 22,
-       FMT_INT8F = 23, FMT_INT4F = 24, FMT_INT2F = 25 };
+       FMT_INT8F = 23, FMT_INT4F = 24, FMT_INT2F = 25, FMT_NVFP4 = 26 };
 // Outlier rows (FMT_INT8O / FMT_INT4O / FMT_INT2O; codec/wire.py with_outliers resolves the int classes of a per-token
 // codec to them): [the plain twin's code bytes][8 fp32 values][8 uint16 channels], the twin's bytes + OUT_TAIL.  The 8
 // channels with the largest abs_bits(x) (NaN > Inf > finite; ties to the lower channel), listed in that order, cross
@@ -172,6 +172,27 @@ constexpr bool rf_size_ok(int H) {   // 2^7 .. 2^12, or 28 * 2^m for m = 5, 6, 7
 // (MXR)`; MXR x MX6 when a class is 6-bit, the only ones of the MXR family with LDS), so the instantiations every
 // other codec runs keep their instruction stream.  Header word 7 is hi_fmt | lo_fmt << 8 as for 6-bit rows, and
 // unpack_kernel<MXR> decodes a message that says otherwise to NaN.  Not next to FMT_GRPR, FMT_F16, FMT_F16S rows.
+// NVFP4 rows (FMT_NVFP4; codec/wire.py with_mx_elem "nvfp4" resolves a codec's FMT_MXFP4 classes to it): E2M1 codes in
+// blocks of 16 consecutive channels, each with an E4M3 scale byte (OCP e4m3fn, bias 7, subnormals kept), and one fp32
+// second-level scale g a row: [H/2 code bytes][H/16 scale bytes][g], 9 H / 16 + 4 bytes, byte-aligned only (H = 32: 22) -
+// the code dwords and g are written and read at any address, as MXFP4 rows' dwords are.  Encode, every step one fp32
+// operation rounded once, `/` the correctly rounded quotient: g = am / 2688 with am the row's max-abs on bit patterns
+// (2688 = 448 * 6: the loudest block's scale is the E4M3 maximum; a NaN / Inf in the row makes g non-finite); per block
+// w = (amb / g) / 6 with amb the block's max-abs, sb = the E4M3 round-to-nearest-even byte of min(w, 448) - the clamp
+// first, the convert does not saturate and (am / g) / 6 can round above 448; g == 0 (an all-zero row) -> sb = 0;
+// d = e4m3(sb) * g; sb == 0 or d < 2^-126 (zero or denormal) -> the block's codes are 0, else code = E2M1 round to
+// nearest, ties to the even code, of clamp(x / d, +-6), the sign kept on what rounds to zero.  Decode: d the same,
+// value = e2m1(code) * d.  No add follows a multiply, so there is nothing for fp contraction to fuse and the CPU oracle
+// (codec/wire.py _nv_pack / _nv_unpack) agrees bit for bit.  The unit of the non-finite rule is the token row: a
+// non-finite g decodes the whole row to NaN (only such a row's code and scale bytes may differ from the CPU's); a NaN w
+// takes the clamp's 448, so the encoder never writes the E4M3 NaN bytes 0x7F / 0xFF - a received one makes d, and with
+// it the block's 16 channels, NaN.  The E2M1 and E4M3 converts run with scale operand 1.0f (a power of two, as every
+// scale operand in this file: what the hardware does with that operand's mantissa bits is not relied on); x / d and
+// code * d are VALU operations.  Where it runs: nv_pack8 / nv_unpack8, in the NV4 instantiations of pack_kernel /
+// unpack_kernel (every such branch under `if constexpr (NV4)`; beside native and plain FMT_MXFP8 rows, not next to
+// head-group, 16-bit, 6-bit, rotated MX, outlier or rotated int rows), so the instantiations every other codec runs
+// keep their instruction stream.  Header word 7 is hi_fmt | lo_fmt << 8 and unpack_kernel<NV4> decodes a message that
+// says otherwise to NaN.
 enum { SC_TOKEN = 0, SC_WINDOW = 1, SC_CHANNEL = 2, SC_NONE = 3 };
 enum { CH_MAXABS = 0, CH_MEAN = 1 };
 
@@ -185,8 +206,11 @@ struct CodecArgs {
   int grp_code_bytes;           // FMT_GRP / FMT_GRPR: sum over groups of 8 b_g (row = codes + 4 G scale bytes)
 };
 
-template <bool W16, bool MX6, bool MXR = false, bool OUT = false, bool RR = false, bool RF = false>
+template <bool W16, bool MX6, bool MXR = false, bool OUT = false, bool RR = false, bool RF = false, bool NV4 = false>
 __device__ __forceinline__ int fmt_row_bytes(int fmt, int H) {
+  if constexpr (NV4) {   // E2M1 codes, one E4M3 scale byte per 16 channels, the row's fp32 g
+    if (fmt == FMT_NVFP4) return 9 * (H / 16) + 4;
+  }
   if constexpr (RF) {    // a row-rotated int row has the bytes of its plain twin
     if (is_rf_fmt(fmt)) return fmt == FMT_INT8F ? H : fmt == FMT_INT4F ? H / 2 : H / 4;
   }
@@ -213,21 +237,23 @@ __device__ __forceinline__ int fmt_row_bytes(int fmt, int H) {
   return fmt == FMT_F32 ? 4 * H : fmt == FMT_BF16 ? 2 * H : fmt == FMT_INT8 ? H : fmt == FMT_INT4 ? H / 2 :
          fmt == FMT_MXFP4 ? H / 2 + H / 32 : fmt == FMT_MXFP8 ? H + H / 32 : H / 4;
 }
-template <bool ROT, bool W16, bool MX6, bool MXR = false, bool OUT = false, bool RR = false, bool RF = false>
+template <bool ROT, bool W16, bool MX6, bool MXR = false, bool OUT = false, bool RR = false, bool RF = false,
+          bool NV4 = false>
 __device__ __forceinline__ int row_bytes(const CodecArgs& a, int fmt) {
   if constexpr (ROT) {
     if (fmt == FMT_GRPR) return a.grp_code_bytes + 4 * (a.H / 64);
   }
-  return fmt == FMT_GRP ? a.grp_code_bytes + 4 * (a.H / 64) : fmt_row_bytes<W16, MX6, MXR, OUT, RR, RF>(fmt, a.H);
+  return fmt == FMT_GRP ? a.grp_code_bytes + 4 * (a.H / 64) : fmt_row_bytes<W16, MX6, MXR, OUT, RR, RF, NV4>(fmt, a.H);
 }
 // Formats whose rows carry their own scales (or none): no entry in the message's scale section.  A macro, and the
 // rotated format joined with `|`: the compiler simplifies the body of an inlined function on its own first, and the
 // rotated pack instantiations then allocate 66 / 82 instead of 56 / 74 VGPRs (NCH 2 / 4: a wave per SIMD less).
-#define SELF_SCALED(ROT, W16, MX6, MXR, fmt) \
+#define SELF_SCALED(ROT, W16, MX6, MXR, NV4, fmt) \
   (((fmt) == FMT_BF16 || (fmt) == FMT_F32 || (fmt) == FMT_MXFP4 || (fmt) == FMT_MXFP8 || (fmt) == FMT_GRP) | \
    ((ROT) && (fmt) == FMT_GRPR) | ((W16) && ((fmt) == FMT_F16 || (fmt) == FMT_F16S)) | \
    ((MX6) && ((fmt) == FMT_MXFP6 || (fmt) == FMT_MXBF6)) | \
-   ((MXR) && ((fmt) == FMT_MXFP4R || (fmt) == FMT_MXFP8R || (fmt) == FMT_MXFP6R || (fmt) == FMT_MXBF6R)))
+   ((MXR) && ((fmt) == FMT_MXFP4R || (fmt) == FMT_MXFP8R || (fmt) == FMT_MXFP6R || (fmt) == FMT_MXBF6R)) | \
+   ((NV4) && (fmt) == FMT_NVFP4))
 
 // Max-abs reductions of the codec propagate NaN (a unit holding a NaN / Inf must decode non-finite, and fmaxf drops a
 // NaN operand): they run on the bit pattern of |x| as an unsigned integer.  For non-negative floats the integer order
@@ -388,20 +414,21 @@ __device__ __forceinline__ void kvar_prefix(const CodecArgs& a, int b, int& Kb, 
 // among the class's rows of its window (lo_prefix), the class's rows of the windows before (b k / b (S - k) for fixed
 // k, the k vector's prefix sum for variable k, whose hi section starts right after the Sum k lo rows).
 struct RowSlot { uint8_t* p; int fmt, qmax, b; };
-template <bool ROT, bool W16, bool MX6, bool MXR = false, bool OUT = false, bool RR = false, bool RF = false>
+template <bool ROT, bool W16, bool MX6, bool MXR = false, bool OUT = false, bool RR = false, bool RF = false,
+          bool NV4 = false>
 __device__ __forceinline__ RowSlot row_slot(const CodecArgs& a, int row) {
   const int b = row / a.S, j = row - b * a.S;
   const uint32_t* mask = (const uint32_t*)(a.msg + a.off_mask) + (size_t)b * a.mw;
   bool is_lo;
   const int slot_lo = lo_prefix(mask, a.mw, j, is_lo);
   const int fmt = is_lo ? a.lo_fmt : a.hi_fmt;
-  const int rb = row_bytes<ROT, W16, MX6, MXR, OUT, RR, RF>(a, fmt);
+  const int rb = row_bytes<ROT, W16, MX6, MXR, OUT, RR, RF, NV4>(a, fmt);
   uint8_t* p;
   if (a.off_kvec >= 0) {
     int Kb, Kt;
     kvar_prefix(a, b, Kb, Kt);
     const long long off_hi =
-        a.off_lo + (((long long)Kt * row_bytes<ROT, W16, MX6, MXR, OUT, RR, RF>(a, a.lo_fmt) + 15) & ~15ll);
+        a.off_lo + (((long long)Kt * row_bytes<ROT, W16, MX6, MXR, OUT, RR, RF, NV4>(a, a.lo_fmt) + 15) & ~15ll);
     p = is_lo ? a.msg + a.off_lo + ((size_t)Kb + slot_lo) * rb
               : a.msg + off_hi + ((size_t)b * a.S - Kb + (j - slot_lo)) * rb;
   } else {
@@ -633,6 +660,64 @@ __device__ __forceinline__ void mx_unpack8_rot(const uint8_t* __restrict__ row, 
   wht_quad(o);
 #pragma unroll
   for (int e = 0; e < 8; ++e) o[e] *= 0.125f;
+}
+
+// NVFP4 rows: a 16-channel block is the lane pair (2 i, 2 i + 1) of a chunk (col = (64 c + lane) 8: block = lane >> 1),
+// so its max-abs is one DPP quad move and a umax, and both lanes of the pair compute the block's scale byte and step
+// from the same operands - identically, with no second exchange.  g, the row's second-level scale, is wave-uniform.
+// Both lanes of a pair must be at the move: H % 32 == 0 makes the col >= H early-out drop whole quads, so whole lane
+// pairs, and a row's format is wave-uniform (row_slot).  No LDS, no shuffle through LDS, no scratch.
+// a row of 9 H / 16 + 4 (or, MXFP6 rows, 25 H / 32) bytes starts on no 4-byte boundary in general: its dword accesses are
+// declared unaligned (gfx950 serves them as dword accesses all the same)
+typedef uint32_t __attribute__((aligned(1))) u32_una_t;
+typedef float __attribute__((aligned(1))) f32_una_t;
+__device__ __forceinline__ float e4m3_value(int sb) {   // the convert with scale 1.0f; bytes 0x7F / 0xFF: NaN
+  return __builtin_amdgcn_cvt_scalef32_pk_f32_fp8((uint32_t)sb, 1.0f, false)[0];
+}
+// The row's g from the bits of its max-abs, in an SGPR (the division runs once per lane all the same: there is no
+// scalar one).
+__device__ __forceinline__ float nv_row_scale(uint32_t amb) {
+  return __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(__uint_as_float(amb) / 2688.0f)));
+}
+struct NvBlock { int sb; float d; bool live; };   // scale byte, step d = e4m3(sb) g, and whether the block has codes
+__device__ __forceinline__ NvBlock nv_block(uint32_t amb, float g) {
+  const float w = (__uint_as_float(amb) / g) / 6.0f;
+  const float wc = w < 448.0f ? w : 448.0f;   // a NaN w (a non-finite row; 0 / 0 of a zero row) takes 448 too
+  s16x2_t p = {0, 0};
+  p = __builtin_amdgcn_cvt_scalef32_pk_fp8_f32(p, wc, wc, 1.0f, false);
+  const int sb = g == 0.f ? 0 : (int)((uint16_t)p[0] & 255u);
+  const float d = e4m3_value(sb) * g;
+  return {sb, d, sb != 0 && !(d < 1.17549435e-38f)};
+}
+__device__ __forceinline__ void nv_pack8(uint8_t* __restrict__ row, int H, int col, const float (&v)[8], float g) {
+  const int lane = threadIdx.x & 63;
+  uint32_t amb = umax8(v);
+  amb = umax(amb, quad_mov<QUAD_X1>(amb));
+  const NvBlock k = nv_block(amb, g);
+  float q[8];
+#pragma unroll
+  for (int e = 0; e < 8; ++e) q[e] = fminf(fmaxf(v[e] / k.d, -6.0f), 6.0f);
+  uint32_t w = 0;
+  w = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(w, q[0], q[1], 1.0f, 0);
+  w = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(w, q[2], q[3], 1.0f, 1);
+  w = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(w, q[4], q[5], 1.0f, 2);
+  w = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(w, q[6], q[7], 1.0f, 3);
+  *(u32_una_t*)(row + col / 2) = k.live ? w : 0u;
+  if ((lane & 1) == 0) row[H / 2 + col / 16] = (uint8_t)k.sb;
+}
+// g: the row's, read once (nv_load_scale); a non-finite one decodes the row to NaN whatever its bytes say
+__device__ __forceinline__ float nv_load_scale(const uint8_t* __restrict__ row, int H) {
+  return __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(*(const f32_una_t*)(row + 9 * (H / 16)))));
+}
+__device__ __forceinline__ void nv_unpack8(const uint8_t* __restrict__ row, int H, int col, float g, float (&o)[8]) {
+  const float d = e4m3_value(row[H / 2 + col / 16]) * g;
+  const uint32_t w = *(const u32_una_t*)(row + col / 2);
+  f32x2_t p0 = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(w, 1.0f, 0), p1 = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(w, 1.0f, 1);
+  f32x2_t p2 = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(w, 1.0f, 2), p3 = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(w, 1.0f, 3);
+  put4(o, p0, p1, p2, p3);
+#pragma unroll
+  for (int e = 0; e < 8; ++e) o[e] *= d;
+  if (!(fabsf(g) < __builtin_inff())) fill8(o, __builtin_nanf(""));
 }
 
 // Rotated per-token int rows: the unnormalised 128-point Walsh-Hadamard transform of a block held 8 consecutive
@@ -892,9 +977,6 @@ constexpr int MX6_PASS(int nch) { return nch < 4 ? nch : 4; }
 typedef __attribute__((ext_vector_type(16))) float f32v16_t;
 typedef __attribute__((ext_vector_type(32))) float f32v32_t;
 typedef __attribute__((ext_vector_type(6))) uint32_t u32x6_t;
-// a row of 25 H / 32 bytes starts on a 4-byte boundary only when H % 128 == 0: its dword accesses are declared unaligned
-// (gfx950 serves them as dword accesses all the same)
-typedef uint32_t __attribute__((aligned(1))) u32_una_t;
 __device__ __forceinline__ void mx6_wave_sync() {
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   __builtin_amdgcn_wave_barrier();
@@ -1323,12 +1405,12 @@ __device__ __forceinline__ float rf_dec_scale(int H) {
 }
 
 template <int NCH, class T, bool ROT = false, bool W16 = false, bool MX6 = false, bool MXR = false, bool OUT = false,
-          bool RR = false, bool RF = false>
+          bool RR = false, bool RF = false, bool NV4 = false>
 __global__ __launch_bounds__(256) void pack_kernel(CodecArgs a) {
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= a.B * a.S) return;
   const int lane = threadIdx.x & 63;
-  const RowSlot rs = row_slot<ROT, W16, MX6, MXR, OUT, RR, RF>(a, row);
+  const RowSlot rs = row_slot<ROT, W16, MX6, MXR, OUT, RR, RF, NV4>(a, row);
   uint8_t* dst = rs.p;
   const bool orow = OUT && is_out_fmt(rs.fmt);   // an outlier row: fmt is its plain twin's
   const bool rrow = RR && is_rr_fmt(rs.fmt);     // a rotated int row: fmt is its plain twin's
@@ -1361,7 +1443,7 @@ __global__ __launch_bounds__(256) void pack_kernel(CodecArgs a) {
 
   // scale / quantiser for this row
   float inv = 0.f, mul = 0.f;  // code = round(x * inv) for token & channel; window mode uses ref formula
-  const bool raw = SELF_SCALED(ROT, W16, MX6, MXR, fmt);
+  const bool raw = SELF_SCALED(ROT, W16, MX6, MXR, NV4, fmt);
   if (raw && a.scale_mode == SC_TOKEN && lane == 0) scales[row] = 0.f;
   if (!raw) {
     if (a.scale_mode == SC_TOKEN) {
@@ -1415,6 +1497,16 @@ __global__ __launch_bounds__(256) void pack_kernel(CodecArgs a) {
       if (lane == 0) *(float*)(dst + 2 * a.H) = k.p;
     }
   }
+  float nvg = 0.f;     // FMT_NVFP4: the row's second-level scale g
+  if constexpr (NV4) {
+    if (fmt == FMT_NVFP4) {
+      uint32_t amb = 0;
+#pragma unroll
+      for (int c = 0; c < NCH; ++c) amb = umax(amb, umax8(v[c]));
+      nvg = nv_row_scale(wave_umax(amb));
+      if (lane == 0) *(f32_una_t*)(dst + 9 * (a.H / 16)) = nvg;
+    }
+  }
 #pragma unroll
   for (int c = 0; c < NCH; ++c) {
     const int col = (c * 64 + lane) * 8;
@@ -1432,6 +1524,12 @@ __global__ __launch_bounds__(256) void pack_kernel(CodecArgs a) {
     if constexpr (MXR) {   // all 4 lanes of the block's quad are here (wht_quad)
       if (fmt == FMT_MXFP4R || fmt == FMT_MXFP8R) {
         mx_pack8_rot(dst, a.H, col, fmt == FMT_MXFP4R ? FMT_MXFP4 : FMT_MXFP8, v[c]);
+        continue;
+      }
+    }
+    if constexpr (NV4) {   // both lanes of the block's pair are here (nv_pack8)
+      if (fmt == FMT_NVFP4) {
+        nv_pack8(dst, a.H, col, v[c], nvg);
         continue;
       }
     }
@@ -1600,12 +1698,12 @@ __device__ __forceinline__ void mx6_unpack_row(const uint8_t* __restrict__ row, 
 }
 
 template <int NCH, class T, bool ROT = false, bool W16 = false, bool MX6 = false, bool MXR = false, bool OUT = false,
-          bool RR = false, bool RF = false>
+          bool RR = false, bool RF = false, bool NV4 = false>
 __global__ __launch_bounds__(256) void unpack_kernel(CodecArgs a) {
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= a.B * a.S) return;
   const int lane = threadIdx.x & 63;
-  const RowSlot rs = row_slot<ROT, W16, MX6, MXR, OUT, RR, RF>(a, row);
+  const RowSlot rs = row_slot<ROT, W16, MX6, MXR, OUT, RR, RF, NV4>(a, row);
   const uint8_t* src = rs.p;
   const bool orow = OUT && is_out_fmt(rs.fmt);   // an outlier row: fmt is its plain twin's
   const bool rrow = RR && is_rr_fmt(rs.fmt);     // a rotated int row: fmt is its plain twin's
@@ -1613,13 +1711,13 @@ __global__ __launch_bounds__(256) void unpack_kernel(CodecArgs a) {
   const int fmt = rf_twin<RF>(rr_twin<RR>(out_twin<OUT>(rs.fmt))), qmax = rs.qmax, b = rs.b;
   const float* scales = (const float*)(a.msg + a.off_scale);
   float s = 0.f;
-  if (!SELF_SCALED(ROT, W16, MX6, MXR, fmt)) {
+  if (!SELF_SCALED(ROT, W16, MX6, MXR, NV4, fmt)) {
     if (a.scale_mode == SC_TOKEN) s = scales[row];
     else if (a.scale_mode == SC_WINDOW) s = scales[b];
   }
   T* out = (T*)a.x + (size_t)row * a.H;
-  if constexpr (MX6 || MXR || OUT || RR || RF) {
-    // header word 7 of a message with 6-bit, rotated or outlier rows names both classes' formats; one that disagrees with the
+  if constexpr (MX6 || MXR || OUT || RR || RF || NV4) {
+    // header word 7 of a message with 6-bit, rotated, outlier or NVFP4 rows names both classes' formats; one that disagrees with the
     // formats this launch was given (encoded with another element type, or without the modifier) decodes to NaN - loud
     if (((const int*)a.msg)[7] != (a.hi_fmt | a.lo_fmt << 8)) {
       float o[8];
@@ -1661,6 +1759,10 @@ __global__ __launch_bounds__(256) void unpack_kernel(CodecArgs a) {
   if constexpr (OUT) {
     if (orow) op = out_load(src + fmt_row_bytes<false, false>(fmt, a.H), a.H);   // wave-uniform: the row's format
   }
+  float nvg = 0.f;     // FMT_NVFP4: the row's second-level scale g
+  if constexpr (NV4) {
+    if (fmt == FMT_NVFP4) nvg = nv_load_scale(src, a.H);
+  }
 #pragma unroll
   for (int c = 0; c < NCH; ++c) {
     const int col = (c * 64 + lane) * 8;
@@ -1697,6 +1799,14 @@ __global__ __launch_bounds__(256) void unpack_kernel(CodecArgs a) {
       if (fmt == FMT_MXFP4R || fmt == FMT_MXFP8R) {
         float o[8];
         mx_unpack8_rot(src, a.H, col, fmt == FMT_MXFP4R ? FMT_MXFP4 : FMT_MXFP8, o);
+        store8(out + col, o);
+        continue;
+      }
+    }
+    if constexpr (NV4) {
+      if (fmt == FMT_NVFP4) {
+        float o[8];
+        nv_unpack8(src, a.H, col, nvg, o);
         store8(out + col, o);
         continue;
       }
@@ -2090,11 +2200,11 @@ EDGE_API int edge_rowmax(const float* in, float* out, int R, int H, hipStream_t 
 static bool has_fmt(int hi_fmt, int lo_fmt, int fmt) { return hi_fmt == fmt || lo_fmt == fmt; }
 
 template <bool PACK, int NCH, class T, bool ROT, bool W16 = false, bool MX6 = false, bool MXR = false, bool OUT = false,
-          bool RR = false, bool RF = false>
+          bool RR = false, bool RF = false, bool NV4 = false>
 static void launch_codec(dim3 grid, hipStream_t st, const CodecArgs& a) {
   if constexpr (PACK)
-    hipLaunchKernelGGL((pack_kernel<NCH, T, ROT, W16, MX6, MXR, OUT, RR, RF>), grid, dim3(256), 0, st, a);
-  else hipLaunchKernelGGL((unpack_kernel<NCH, T, ROT, W16, MX6, MXR, OUT, RR, RF>), grid, dim3(256), 0, st, a);
+    hipLaunchKernelGGL((pack_kernel<NCH, T, ROT, W16, MX6, MXR, OUT, RR, RF, NV4>), grid, dim3(256), 0, st, a);
+  else hipLaunchKernelGGL((unpack_kernel<NCH, T, ROT, W16, MX6, MXR, OUT, RR, RF, NV4>), grid, dim3(256), 0, st, a);
 }
 
 // edge_pack / edge_unpack: argument checks, CodecArgs and the (ROT | W16 | plain) x activation dtype x NCH dispatch.
@@ -2107,7 +2217,9 @@ static void launch_codec(dim3 grid, hipStream_t st, const CodecArgs& a) {
 // RR instantiations; with H % 128 != 0, any scale mode but SC_TOKEN, or next to head-group, 16-bit, 6-bit, rotated MX or
 // outlier rows, it is rejected the same way.  A message with row-rotated int rows goes to the RF instantiations; with a
 // hidden size that is neither 2^7 .. 2^12 nor 28 * 2^5 .. 28 * 2^7, any scale mode but SC_TOKEN, or next to head-group,
-// 16-bit, 6-bit, rotated MX, outlier or block-rotated (h128) rows, it is rejected the same way.
+// 16-bit, 6-bit, rotated MX, outlier or block-rotated (h128) rows, it is rejected the same way.  A message with NVFP4
+// rows goes to the NV4 instantiations; next to head-group, 16-bit, 6-bit, rotated MX, outlier, h128 or row-rotated rows
+// it is rejected the same way.
 template <bool PACK>
 static int run_codec(void* x, void* msg, long long om, long long os, long long oh, long long ol, long long okv,
                      long long opl, int B, int S, int H, int k, int hi_fmt, int lo_fmt, int scale_mode, int qmax_hi,
@@ -2131,6 +2243,9 @@ static int run_codec(void* x, void* msg, long long om, long long os, long long o
                   has_fmt(hi_fmt, lo_fmt, FMT_INT2F);
   if (rf && (rr || out || rot || w16 || mx6 || mxr || has_fmt(hi_fmt, lo_fmt, FMT_GRP) || scale_mode != SC_TOKEN ||
              !rf_size_ok(H)))
+    return (int)hipErrorInvalidValue;
+  const bool nv4 = has_fmt(hi_fmt, lo_fmt, FMT_NVFP4);
+  if (nv4 && (rf || rr || out || rot || w16 || mx6 || mxr || has_fmt(hi_fmt, lo_fmt, FMT_GRP)))
     return (int)hipErrorInvalidValue;
   if ((rot || has_fmt(hi_fmt, lo_fmt, FMT_GRP)) && (H % 64 || opl < 0 || grp_code_bytes <= 0))
     return (int)hipErrorInvalidValue;
@@ -2163,6 +2278,10 @@ static int run_codec(void* x, void* msg, long long om, long long os, long long o
     DISPATCH_NCH(H, (launch_codec<PACK, NCH, float, false, false, false, false, false, false, true>(grid, st, a)));
   else if (rf)
     DISPATCH_NCH(H, (launch_codec<PACK, NCH, bf16_t, false, false, false, false, false, false, true>(grid, st, a)));
+  else if (nv4 && x_f32)
+    DISPATCH_NCH(H, (launch_codec<PACK, NCH, float, false, false, false, false, false, false, false, true>(grid, st, a)));
+  else if (nv4)
+    DISPATCH_NCH(H, (launch_codec<PACK, NCH, bf16_t, false, false, false, false, false, false, false, true>(grid, st, a)));
   else if (x_f32) DISPATCH_NCH(H, (launch_codec<PACK, NCH, float, false>(grid, st, a)));
   else DISPATCH_NCH(H, (launch_codec<PACK, NCH, bf16_t, false>(grid, st, a)));
   return (int)hipGetLastError();

@@ -28,6 +28,8 @@ mixed_mxfp4_mxfp8      MXFP8 (E4M3)    MXFP4 (E2M1)    E8M0 / 32ch  configs 3-5 
 mxfp4_keep             native dtype    MXFP4           E8M0 / 32ch  Q1 with MX blocks instead of one scale
 (the three above)      with_mx_elem "e2m3" / "e3m2": their MXFP4    MXFP6 rows, 6.25 bits per element
                        rows as FP6 E2M3 / E3M2 codes                (gfx950 2xpk16 / pk32 fp6 converts)
+(the three above)      with_mx_elem "nvfp4": their MXFP4 rows as    E2M1 codes, an E4M3 scale per 16 channels,
+                       NVFP4 rows, 4.5 bits per element             one fp32 scale a row (lane pairs, one DPP move)
 (the four above)       with_mx_rot "h32": their MX rows as the      the plain rows' bytes of y = H32 x / 4 per
                        rotated twins of the same element type       32-channel block (Hadamard, quad DPP moves)
 (the int rows above)   with_outliers "top8": the int8 / int4 /      the row's 8 largest channels cross as exact
@@ -64,7 +66,9 @@ see ``wire.py``.  BASELINE config 1 ("fp16 pass-through") is ``passthrough`` wit
 ``with_mx_elem(spec, "e2m3" | "e3m2")`` (params key ``mx_elem``) fills the MX family's gap between 4.25 (``mxfp4``) and
 8.25 (``mxfp8``) bits per element: the codec's MXFP4 rows become MXFP6 rows - 32-channel E8M0 blocks of FP6 E2M3 (max
 7.5) or E3M2 (max 28) codes, 25 H / 32 bytes a row.  A modifier like ``with_native_wire``, not a new codec; not combined
-with a 16-bit native wire.
+with a 16-bit native wire.  ``with_mx_elem(spec, "nvfp4")`` sends the same rows as NVFP4 rows instead: E2M1 codes in
+blocks of 16 channels with an E4M3 scale each and one fp32 scale a row, 9 H / 16 + 4 bytes - the point between ``fp4``
+and ``e2m3``; not combined with ``with_mx_rot`` either.
 
 ``with_mx_rot(spec, "h32")`` (params key ``mx_rot``) puts a 32-point Hadamard transform in front of every MX block's
 quantizer and behind its dequantizer, at the plain row's bytes: one loud channel of a block no longer sets the scale

@@ -121,6 +121,32 @@ decoded row non-finite.  Header word 7, the refusals and the combinations are ``
 wherever ``h128`` is ahead of the plain row, and further behind where rotation loses (int4 with a x1000 channel, int2):
 that regime is ``with_outliers``'.
 
+NVFP4 rows.  ``with_mx_elem(spec, "nvfp4")`` - the same option's fourth value - resolves the same ``FMT_MXFP4`` classes to
+``FMT_NVFP4`` = 26: E2M1 codes in blocks of 16 channels, each with an E4M3 scale (OCP e4m3fn, bias 7, 3 mantissa bits,
+subnormals kept) instead of MXFP4's power of two shared by 32, and one fp32 second-level scale ``g`` a row that keeps the
+E4M3 scales in range: 4.5 bits per element plus 32 / H.  The row is self-scaled::
+
+    [H/2 code bytes][H/16 E4M3 scale bytes][g: one fp32, little-endian]        9H/16 + 4 bytes  (H = 896: 508)
+
+Channel 2p is the low nibble of byte p; the scale byte of block j (channels [16j, 16j + 16)) is byte ``H/2 + j``; rows
+are byte-aligned only.  Encode, every step one fp32 operation rounded once, ``/`` the correctly rounded quotient:
+
+1. ``g = am / 2688`` with ``am`` the row's max-abs (2688 = 448 x 6: the loudest block's scale is the E4M3 maximum).  A
+   NaN / Inf in the row makes ``g`` non-finite.
+2. per block ``w = (amb / g) / 6`` with ``amb`` the block's max-abs, and ``sb`` the E4M3 round-to-nearest-even byte of
+   ``min(w, 448)`` (the clamp first: the convert does not saturate; a NaN ``w`` takes 448 too, so the bytes 0x7F / 0xFF
+   are never written).  ``g == 0`` (an all-zero row): every ``sb`` and code is 0.
+3. ``d = e4m3(sb) * g``.  ``sb == 0`` or ``d < 2^-126``: the block's codes are 0.  Otherwise code = E2M1 round to nearest,
+   ties to the even code, of ``clamp(x / d, +-6)``, the sign kept on values that round to zero.
+
+Decode: ``d`` as in step 3 from the stored bytes, value = ``e2m1(code) * d``.  No add follows a multiply.  The unit of
+the non-finite rule is the token row: a row whose ``g`` is non-finite decodes to NaN throughout, and only its code and
+scale bytes may differ between GPU and CPU; a received scale byte 0x7F / 0xFF decodes its 16 channels to NaN.  Rows with
+a max-abs near 2^-126 and below fall under ``d < 2^-126`` and decode to +0: finite and bounded, not accurate.  Header
+word 7 is ``hi_fmt | lo_fmt << 8`` and ``decode`` refuses a message whose formats are not its spec's.  Not combined with
+``native_wire`` 16-bit rows, ``mx_rot`` (rotation of 16-channel blocks is out of scope), ``outliers`` or ``row_rot``; such
+specs are not served by ``fake_quant_fork``.
+
 ``encode``/``decode`` run the gfx950 kernels of ``csrc/codec.hip`` for CUDA
 tensors and a bit-identical PyTorch implementation for CPU tensors.
 
@@ -156,6 +182,8 @@ FMT_INT8R, FMT_INT4R, FMT_INT2R = 20, 21, 22   # per-token int rows of the Hadam
 ROW_ROT_TWIN = {FMT_INT8: FMT_INT8R, FMT_INT4: FMT_INT4R, FMT_INT2: FMT_INT2R}
 FMT_INT8F, FMT_INT4F, FMT_INT2F = 23, 24, 25   # per-token int rows of the Hadamard-rotated whole row (with_row_rot "full")
 ROW_ROT_FULL_TWIN = {FMT_INT8: FMT_INT8F, FMT_INT4: FMT_INT4F, FMT_INT2: FMT_INT2F}
+FMT_NVFP4 = 26              # E2M1 codes in 16-channel blocks with E4M3 scales and one fp32 scale a row (with_mx_elem "nvfp4")
+NV_FORMATS = (FMT_NVFP4,)   # not in MX_FORMATS: those rows have E8M0 scale bytes
 ROW_ROT_FULL = -1           # CodecSpec.row_rot of "full": the block is the row
 ROW_ROT_FULL_SIZES = tuple(1 << n for n in range(7, 13)) + tuple(28 << m for m in (5, 6, 7))   # 2^n; 28 * 2^m
 GRP_FORMATS = (FMT_GRP, FMT_GRPR)
@@ -163,7 +191,7 @@ SC_TOKEN, SC_WINDOW, SC_CHANNEL, SC_NONE = 0, 1, 2, 3
 CH_MAXABS, CH_MEAN = 0, 1
 NATIVE = -1  # "keep in the activation dtype" (bf16 on GPU, fp32 in the CPU reference mode)
 NATIVE_WIRES = {"native": NATIVE, "bf16": FMT_BF16, "fp16": FMT_F16, "fp16s": FMT_F16S}   # with_native_wire
-MX_ELEMS = {"fp4": FMT_MXFP4, "e2m3": FMT_MXFP6, "e3m2": FMT_MXBF6}                         # with_mx_elem
+MX_ELEMS = {"fp4": FMT_MXFP4, "e2m3": FMT_MXFP6, "e3m2": FMT_MXBF6, "nvfp4": FMT_NVFP4}     # with_mx_elem
 MX_ROTS = {"none": 0, "h32": 32}                                                            # with_mx_rot: block size
 OUTLIERS = {"none": 0, "top8": OUT_K}                                                       # with_outliers: count
 ROW_ROTS = {"none": 0, "h128": 128, "full": ROW_ROT_FULL}                                   # with_row_rot: block size
@@ -254,7 +282,7 @@ def with_native_wire(spec: CodecSpec, name: str) -> CodecSpec:
         raise ValueError(f"codec {spec.name} keeps no rows in the activation dtype: native_wire {name!r} has nothing "
                          "to apply to")
     if name != "native" and spec.mx_elem != FMT_MXFP4:
-        raise ValueError(f"native_wire {name!r} is not combined with 6-bit MX rows (mx_elem)")
+        raise ValueError(f"native_wire {name!r} is not combined with 6-bit MX or NVFP4 rows (mx_elem)")
     if name != "native" and spec.mx_rot:
         raise ValueError(f"native_wire {name!r} is not combined with rotated MX rows (mx_rot)")
     if name != "native" and spec.outliers:
@@ -266,8 +294,8 @@ def with_native_wire(spec: CodecSpec, name: str) -> CodecSpec:
 
 def with_mx_elem(spec: CodecSpec, name: str) -> CodecSpec:
     """The codec with its FMT_MXFP4 rows sent with element type ``name``: "fp4" (E2M1, the spec itself) | "e2m3" |
-    "e3m2" (MXFP6 rows, module docstring).  A codec without FMT_MXFP4 rows takes "fp4" only; a 6-bit element type is
-    not combined with a 16-bit native wire."""
+    "e3m2" (MXFP6 rows) | "nvfp4" (NVFP4 rows; module docstring).  A codec without FMT_MXFP4 rows takes "fp4" only; no
+    other element type is combined with a 16-bit native wire, and "nvfp4" not with rotated MX rows."""
     from dataclasses import replace
     if name not in MX_ELEMS:
         raise ValueError(f"mx_elem must be one of {tuple(MX_ELEMS)}, got {name!r}")
@@ -280,6 +308,8 @@ def with_mx_elem(spec: CodecSpec, name: str) -> CodecSpec:
             raise ValueError(f"mx_elem {name!r} is not combined with outlier rows (outliers)")
         if spec.row_rot:
             raise ValueError(f"mx_elem {name!r} is not combined with rotated int rows (row_rot)")
+        if MX_ELEMS[name] in NV_FORMATS and spec.mx_rot:
+            raise ValueError(f"mx_elem {name!r} is not combined with rotated MX rows (mx_rot)")
     return spec if spec.mx_elem == MX_ELEMS[name] else replace(spec, mx_elem=MX_ELEMS[name])
 
 
@@ -303,6 +333,8 @@ def with_mx_rot(spec: CodecSpec, name: str) -> CodecSpec:
             raise ValueError(f"mx_rot {name!r} is not combined with outlier rows (outliers)")
         if spec.row_rot:
             raise ValueError(f"mx_rot {name!r} is not combined with rotated int rows (row_rot)")
+        if spec.mx_elem in NV_FORMATS:
+            raise ValueError(f"mx_rot {name!r} is not combined with NVFP4 rows (mx_elem nvfp4)")
     return spec if spec.mx_rot == MX_ROTS[name] else replace(spec, mx_rot=MX_ROTS[name])
 
 
@@ -688,6 +720,37 @@ def _mx_unpack(b: torch.Tensor, fmt: int, n: int, H: int) -> torch.Tensor:
     return torch.where((sb == MX_NAN)[..., None], torch.full_like(out, float("nan")), out).reshape(n, H)
 
 
+# ---- NVFP4 rows (csrc/codec.hip nv_block / nv_pack8 / nv_unpack8) ---------------------------------------------
+NV_BLOCK = 16               # channels per E4M3 scale
+
+
+def _nv_step(sb: torch.Tensor, g: torch.Tensor) -> torch.Tensor:
+    """d = e4m3(sb) * g of scale bytes [n, H/16] and the rows' g [n]: one fp32 multiply."""
+    return sb.contiguous().view(torch.float8_e4m3fn).float() * g[:, None]
+
+
+def _nv_pack(rows: torch.Tensor) -> torch.Tensor:
+    n, H = rows.shape
+    blk = rows.float().reshape(n, H // NV_BLOCK, NV_BLOCK)
+    g = rows.float().abs().amax(-1) / 2688.0                                 # NaN if the row holds one
+    w = (blk.abs().amax(-1) / g[:, None]) / 6.0
+    w = torch.where(w < 448.0, w, torch.full_like(w, 448.0))                 # the clamp; a NaN w takes 448 too
+    sb = torch.where((g == 0)[:, None], torch.zeros_like(w), w).to(torch.float8_e4m3fn).view(torch.uint8)
+    d = _nv_step(sb, g)
+    c = _fp4_codes((blk / d[..., None]).clamp(-6.0, 6.0))
+    c = torch.where(((sb == 0) | (d < 2.0 ** -126))[..., None], torch.zeros_like(c), c).reshape(n, H // 2, 2)
+    return torch.cat([(c[..., 0] | (c[..., 1] << 4)).to(torch.uint8), sb, _bytes(g).reshape(n, 4)], 1).reshape(-1)
+
+
+def _nv_unpack(b: torch.Tensor, n: int, H: int) -> torch.Tensor:
+    r = b.reshape(n, -1)
+    codes, sb, g = r[:, :H // 2], r[:, H // 2:H // 2 + H // NV_BLOCK], r[:, -4:].contiguous().view(torch.float32)[:, 0]
+    c = torch.stack([codes & 15, codes >> 4], -1).reshape(n, H).to(torch.int64)
+    v = _FP4_GRID[c & 7] * torch.where(c >= 8, -1.0, 1.0)
+    out = (v.reshape(n, H // NV_BLOCK, NV_BLOCK) * _nv_step(sb, g)[..., None]).reshape(n, H)
+    return torch.where(torch.isfinite(g)[:, None], out, torch.full_like(out, float("nan")))
+
+
 def _grp_bits_pack(q: torch.Tensor, bits: int) -> torch.Tensor:
     """Codes [n, 64] (two's complement, |q| < 2^(bits-1)) -> the group's little-endian bit stream [n, 8 bits] bytes:
     code c at bits [bits c, bits c + bits); 8 consecutive codes are ``bits`` whole bytes (csrc/codec.hip grp_pack8)."""
@@ -1011,6 +1074,8 @@ ROW_FORMATS = {
     FMT_MXFP6: _mx_rows(FMT_MXFP6, 6), FMT_MXBF6: _mx_rows(FMT_MXBF6, 6),
     FMT_MXFP4R: _mx_rows(FMT_MXFP4, 4, True), FMT_MXFP8R: _mx_rows(FMT_MXFP8, 8, True),
     FMT_MXFP6R: _mx_rows(FMT_MXFP6, 6, True), FMT_MXBF6R: _mx_rows(FMT_MXBF6, 6, True),
+    FMT_NVFP4: RowFormat(lambda H, plan: 9 * H // 16 + 4, True, lambda rows, c: _nv_pack(rows),
+                         lambda raw, n, c: _nv_unpack(raw, n, c.H)),
     FMT_GRP: _grp_rows(False), FMT_GRPR: _grp_rows(True),
     FMT_F16: RowFormat(lambda H, plan: 2 * H, True, lambda rows, c: _bytes(rows.to(torch.float16)),
                        lambda raw, n, c: raw.view(torch.float16).reshape(n, c.H).float()),

@@ -51,7 +51,8 @@ class Params:
                                              # fp32 in the fp32 mode) | "bf16" | "fp16" | "fp16s" (codec/wire.py
                                              # with_native_wire); BASELINE config 1 literally: passthrough + "fp16"
     mx_elem: str = "fp4"                     # element type of a codec's MXFP4 rows: "fp4" (E2M1) | "e2m3" | "e3m2" (MXFP6
-                                             # rows, 6.25 bits per element; codec/wire.py with_mx_elem)
+                                             # rows, 6.25 bits per element) | "nvfp4" (16-channel blocks with E4M3
+                                             # scales, 4.5 bits per element; codec/wire.py with_mx_elem)
     mx_rot: str = "none"                     # "h32": a codec's MX rows quantize the 32-point Hadamard transform of
                                              # every block (codec/wire.py with_mx_rot); "none": the blocks themselves
     outliers: str = "none"                   # "top8": a per-token int codec sends the 8 largest channels of every int

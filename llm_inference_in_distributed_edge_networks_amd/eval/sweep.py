@@ -67,7 +67,7 @@ class SweepConfig:
     group_avg_bits: float = 4.0
     group_plan: str = "auto"           # "measured": exact allocation against the measured quantization error
     native_wire: str = "native"        # the codecs' activation-dtype rows on the wire (codec.wire.with_native_wire)
-    mx_elem: str = "fp4"               # element type of the codecs' MXFP4 rows (codec.wire.with_mx_elem)
+    mx_elem: str = "fp4"               # the codecs' MXFP4 rows as fp4 | e2m3 | e3m2 | nvfp4 (codec.wire.with_mx_elem)
     mx_rot: str = "none"               # "h32": the codecs' MX rows in the Hadamard basis (codec.wire.with_mx_rot)
     outliers: str = "none"             # "top8": the codecs' per-token int rows + 8 exact channels (with_outliers)
     row_rot: str = "none"              # "h128" / "full": the codecs' per-token int rows in the Hadamard basis of every

@@ -50,7 +50,7 @@ class BoundaryConfig:
     group_avg_bits: float = 4.0
     group_plan: str = "auto"      # "measured": exact allocation against the tables' measured quantization error
     native_wire: str = "native"   # the codec's activation-dtype rows on the wire: "native" | "bf16" | "fp16" | "fp16s"
-    mx_elem: str = "fp4"          # element type of the codec's MXFP4 rows: "fp4" | "e2m3" | "e3m2" (MXFP6 rows)
+    mx_elem: str = "fp4"          # element type of the codec's MXFP4 rows: "fp4" | "e2m3" | "e3m2" (MXFP6 rows) | "nvfp4"
     mx_rot: str = "none"          # "h32": the codec's MX rows quantize the Hadamard-rotated blocks (with_mx_rot)
     outliers: str = "none"        # "top8": the codec's per-token int rows carry their 8 largest channels exactly
     row_rot: str = "none"         # "h128": the codec's per-token int rows quantize the Hadamard-rotated 128-channel blocks;

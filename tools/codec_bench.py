@@ -4,9 +4,11 @@
     python tools/codec_bench.py --codecs passthrough,passthrough@bf16,passthrough@fp16,passthrough@fp16s
 
     python tools/codec_bench.py --codecs mxfp8,mxfp4@e2m3,mxfp4@e3m2,mxfp4
+    python tools/codec_bench.py --codecs mxfp4,mxfp4@nvfp4 --hidden 4096
 
 ``name@wire`` is codec ``name`` with its activation-dtype rows on the 16-bit wire ``wire`` (``with_native_wire``),
-``name@e2m3`` / ``name@e3m2`` with its MXFP4 rows as MXFP6 rows of that element type (``with_mx_elem``), ``name@rot``
+``name@e2m3`` / ``name@e3m2`` with its MXFP4 rows as MXFP6 rows of that element type, ``name@nvfp4`` with them as NVFP4
+rows (``with_mx_elem``), ``name@rot``
 with its MX rows Hadamard-rotated (``with_mx_rot``), ``name@top8`` with the 8 largest channels of its per-token int
 rows kept exact (``with_outliers``), ``name@h128`` / ``name@full`` with those rows Hadamard-rotated per 128-channel block /
 as whole rows (``with_row_rot``); modifiers chain: ``mxfp4@e2m3@rot``.

@@ -140,7 +140,8 @@ def main():
         # head-group codecs: "name@bits" = plans of that average width allocated over the groups' sensitivity (MSE),
         # "name@bitsr" = over the LRP relevance (round 3's first-order allocator), "name@bitsu" = the same width in
         # every group (uniform plan, the ablation).  MX codecs: "name@e2m3" / "name@e3m2" = MXFP6 rows of that element
-        # type, "name@rot" = Hadamard-rotated MX rows; they chain ("mxfp4@e2m3@rot").  Per-token int codecs: "name@top8" =
+        # type, "name@nvfp4" = NVFP4 rows, "name@rot" = Hadamard-rotated MX rows; they chain ("mxfp4@e2m3@rot"; not nvfp4
+        # with rot).  Per-token int codecs: "name@top8" =
         # outlier rows, "name@h128" / "name@full" = Hadamard-rotated int rows (blocks / whole row)
         base, *mods = codec.split("@")
         elem = next((x for x in mods if x in C.wire.MX_ELEMS), "fp4")
